@@ -3,26 +3,34 @@
 1024x1024 batches, 16 images per GPU (BASELINE.json config 2; config 3 at --gpus 8).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 16] [--res 1024] [--amp fp16|bf16|none]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line; its only check is the rank
+consistency record below.  ``--dump-outputs DIR`` also writes what the last timed step computed (its loss, the
+gradients and the updated parameters; see dump_outputs) as DIR/<name>.npy; model, inputs and the sampled
+positions are seeded, so two builds run with the same arguments can be compared file by file.  ``--full`` adds,
+after the timed steps, the measurements marked (--full) below, each in runs of its own; without it their fields
+are null or empty.
 
 One process per GPU.  ``--gpus N`` with N > 1 outside torch.distributed.run starts
 ``python -m torch.distributed.run --nproc-per-node N`` itself (before touching the GPU) and exits with its
 status; under torchrun (WORLD_SIZE set) N must equal WORLD_SIZE.  Gradients are all-reduced by DDP over
 RCCL (backend "nccl"), the only exchange on this path.  Rank 0 prints ONE JSON line.
 Besides the contract fields it reports:
-  roofline      the MSDA backward kernel (the hot path's dominant hand-written kernel): algorithmic bytes
+  roofline      (--full) the MSDA backward kernel (the hot path's dominant hand-written kernel): algorithmic bytes
                 per launch (115.60 MB per 1024^2 image) / its mean duration, measured with HIP
                 events on the launch stream, vs the 8 TB/s HBM peak; traffic = PMC-measured HBM bytes per
                 launch (profiles/msda_bwd_traffic.json).
-  roofline_all  the same for every hand-written kernel family (HBM- or MFMA-bound as DESIGN.md §3 says),
+  roofline_all  (--full) the same for every hand-written kernel family (HBM- or MFMA-bound as DESIGN.md §3 says),
                 from extra instrumented steps after the timed region (the timed steps carry no events).
   The headline runs under AMP fp16 with a GradScaler, the reference's training precision
   (Base-COCO-PanopticSegmentation.yaml SOLVER.AMP.ENABLED; detectron2's AMPTrainer).
-  modes         N=1 only: the same step under AMP bf16 (no scaler) and with no autocast at all (fp32 parity
+  modes         (--full) N=1 only: the same step under AMP bf16 (no scaler) and with no autocast at all (fp32 parity
                 mode), fewer steps.
-  achievable    N=1 only: measured ceilings on this box -- a float4 stream copy (m2f_stream_copy,
+  achievable    (--full) N=1 only: measured ceilings on this box -- a float4 stream copy (m2f_stream_copy,
                 2 x 2 GiB per launch) and an 8192^3 bf16 GEMM (hipBLASLt via torch.matmul) -- so each roofline
                 entry carries its fraction of the spec peak (frac) and of the measured one (frac_achievable).
-  cpu_baseline  the reference's CPU path (oracle/cpu_path.py) on config 1 (1 x 512^2) and one 1024^2 image,
+  cpu_baseline  (--full) the reference's CPU path (oracle/cpu_path.py) on config 1 (1 x 512^2) and one 1024^2 image,
                 warm-up 1, median of 3, rank 0, N=1; value = the 1024^2 img/s.
   world_seen / ranks_agree / rank_check
                 the process group's size as RCCL saw it (dist.get_world_size()), and whether every replica holds
@@ -70,13 +78,19 @@ def parse_args(argv=None):
     ap.add_argument("--res", type=int, default=1024)
     ap.add_argument("--queries", type=int, default=None, help="default 100 (configs 2, 5) / 200 (config 4)")
     ap.add_argument("--amp", default="fp16", choices=["fp16", "bf16", "none"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-modes", action="store_true", help="skip the bf16 / fp32 mode lines")
-    ap.add_argument("--no-peaks", action="store_true", help="skip the achievable-peak probes")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the op-level MSDeformAttnFunction timing")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure roofline / roofline_all, achievable, msda_op_dropin, modes "
+                         "and cpu_baseline (each in runs of its own); without it these fields are null or empty")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss, gradients, updated "
+                         "parameters) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-modes", action="store_true", help="--full: skip the bf16 / fp32 mode lines")
+    ap.add_argument("--no-peaks", action="store_true", help="--full: skip the achievable-peak probes")
+    ap.add_argument("--no-dropin", action="store_true", help="--full: skip the op-level MSDeformAttnFunction timing")
     ap.add_argument("--mode-steps", type=int, default=10)
     ap.add_argument("--mode-warmup", type=int, default=3)
-    ap.add_argument("--kernel-steps", type=int, default=2, help="instrumented steps for roofline_all")
+    ap.add_argument("--kernel-steps", type=int, default=2, help="--full: instrumented steps for roofline_all")
     ap.add_argument("--graph", type=int, default=None, choices=[0, 1],
                     help="capture the step in a HIP graph and replay it (default: on for the per-rank configs 4 / 5 "
                          "at one rank, whose small steps are host-launch bound; off for config 2)")
@@ -88,6 +102,9 @@ def parse_args(argv=None):
     ap.add_argument("--allow-knobs", action="store_true")
     ap.add_argument("--master-port", type=int, default=29531)
     a = ap.parse_args(argv)
+    if not a.full:   # a plain run: set up, warm up, time the steps, print the line
+        a.no_cpu_baseline = a.no_modes = a.no_peaks = a.no_dropin = True
+        a.kernel_steps = 0
     if a.batch is None:
         a.batch = 16 if a.config == 2 else 2
     if a.queries is None:
@@ -513,6 +530,35 @@ def load_traffic():
         return None
 
 
+DUMP_SAMPLE = 4 << 20     # elements kept of each dumped vector: 16 MiB of float32 per file
+DUMP_SEED = 20240229
+
+
+def dump_outputs(path, model, loss):
+    """--dump-outputs: what the last timed step handed its caller -- the loss it returned, the gradients it left on
+    the parameters (after unscaling and clipping) and the parameters AdamW then wrote -- as float32 ``loss.npy``,
+    ``grads.npy`` and ``params.npy``.  The two vectors are every parameter's values concatenated in
+    ``model.parameters()`` order (a parameter without a gradient counts as zeros); of a vector longer than
+    DUMP_SAMPLE the same seeded sample of positions is kept on every run, so two builds' files line up."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    params = [p.detach() for p in model.parameters()]
+    grads = [torch.zeros_like(p) if p.grad is None else p.grad.detach() for p in model.parameters()]
+    n = sum(p.numel() for p in params)
+    idx = None
+    if n > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(DUMP_SEED)   # on the host: the same positions whatever the device did
+        idx = torch.randint(n, (DUMP_SAMPLE,), generator=g).sort().values.to(params[0].device)
+    arrays = {"loss": loss.detach().float().reshape(1)}
+    for name, ts in (("grads", grads), ("params", params)):
+        flat = torch.cat([t.reshape(-1).float() for t in ts])
+        arrays[name] = flat if idx is None else flat[idx]
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+    log(f"wrote {', '.join(sorted(arrays))} of the last timed step to {path}")
+
+
 def main():
     args = parse_args()
     # before any HIP call (bm2f_amd/__init__.py): the runtime's graph packet capture replays captured memsets
@@ -594,7 +640,7 @@ def main():
         torch.cuda.synchronize()
         start = last = time.perf_counter()
         for i in range(steps):
-            step_fn()
+            last_loss[tag] = step_fn()
             if time.perf_counter() - last > 30:
                 log(f"{tag} step {i + 1}/{steps}")
                 last = time.perf_counter()
@@ -614,7 +660,10 @@ def main():
 
     graph_info = {}
     rank_times = {}
+    last_loss = {}
     elapsed = run(args.amp, args.steps, args.warmup, "timed", graph=use_graph)
+    if args.dump_outputs and rank == 0 and "timed" in last_loss:
+        dump_outputs(args.dump_outputs, model, last_loss["timed"])
     # config 3 checks itself: after the timed steps every replica must hold bitwise-equal parameters (a parameter
     # DDP failed to reduce, or a rank that fell out of step, shows here), and the process group must be the size
     # the launcher asked for

@@ -342,6 +342,32 @@ def gen_video_decoder_t5(ref, out):
                       name="video_decoder_t5.npz")
 
 
+def gen_state_dict_shapes(ref, out):
+    """Name -> shape of every state_dict entry of the reference's pixel decoder and decoder at the config-2
+    arguments (every entry is a parameter: the filler re-creates such a state_dict from this list alone)."""
+    import json
+    S = ref.ShapeSpec
+    input_shape = {"res2": S(channels=256, stride=4), "res3": S(channels=512, stride=8),
+                   "res4": S(channels=1024, stride=16), "res5": S(channels=2048, stride=32)}
+    mods = {
+        "pixdec": ref.msdeform.MSDeformAttnPixelDecoder(
+            input_shape, transformer_dropout=0.0, transformer_nheads=8, transformer_dim_feedforward=1024,
+            transformer_enc_layers=6, conv_dim=256, mask_dim=256, norm="GN",
+            transformer_in_features=["res3", "res4", "res5"], common_stride=4),
+        "decoder": ref.dec.MultiScaleMaskedTransformerDecoder(
+            256, True, num_classes=133, hidden_dim=256, num_queries=100, nheads=8, dim_feedforward=2048,
+            dec_layers=9, pre_norm=False, mask_dim=256, enforce_input_project=False),
+    }
+    res = {}
+    for name, m in mods.items():
+        assert set(m.state_dict()) == set(dict(m.named_parameters())), name
+        res[name] = {k: list(v.shape) for k, v in sorted(m.state_dict().items())}
+    with open(os.path.join(out, "state_dict_shapes.json"), "w") as f:   # one entry per line
+        f.write("{\n" + ",\n".join(
+            f' "{name}": {{\n' + ",\n".join(f"  {json.dumps(k)}: {json.dumps(v)}" for k, v in d.items()) + "\n }"
+            for name, d in res.items()) + "\n}\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
@@ -351,7 +377,7 @@ def main():
     torch.set_num_threads(min(8, os.cpu_count() or 1))
     ref = import_reference(args.ref)
     for fn in (gen_msda_testpy, gen_msda_slice, gen_pixdec, gen_decoder, gen_decoder_q200, gen_decoder_amp16,
-               gen_video_decoder, gen_video_decoder_t5):
+               gen_video_decoder, gen_video_decoder_t5, gen_state_dict_shapes):
         if args.only and args.only not in fn.__name__:
             continue
         fn(ref, args.out)

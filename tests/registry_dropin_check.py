@@ -1,18 +1,22 @@
-"""Drop-in check of INTEGRATION.md §2, run in a fresh interpreter by tests/test_registry_dropin.py (CPU, this
-container only: it imports the reference from /root/reference, which never travels to the GPU box).
+"""Drop-in check of INTEGRATION.md §2, run in a fresh interpreter by tests/test_registry_dropin.py (CPU).
 
-The order is the one the documented recipe produces: the reference's registry module
-(maskformer_transformer_decoder.py:16) and its own decoder / pixel decoder register first, then bm2f's
+Self-contained: the host framework is stood in for here, with what the check depends on recorded from the reference
+under tests/golden/ (state_dict_shapes.json: the name and shape of every state_dict entry of the reference's pixel
+decoder and decoder; pixdec.npz / decoder.npz: their inputs and outputs).
+
+The order is the one the documented recipe produces: the host's registry module
+(maskformer_transformer_decoder.py:16) and its own decoder / pixel decoder classes register first, then bm2f's
 classes are imported -- as the edited ``__init__.py`` files would import them -- and replace those entries.
-Then the reference's OWN builders, ``build_pixel_decoder`` (pixel_decoder/fpn.py:21-33) and
-``build_transformer_decoder`` (maskformer_transformer_decoder.py:22-27), are called with a config; they must
-return the bm2f classes.  A reference module's state_dict (filled by tests/golden/filler.py, as the fixtures
-were made) loads strictly into each, and the outputs match the reference's golden fixtures on CPU (the
-oracle's MSDA / decoder restatements stand in for the HIP kernels here).
+Then the host's builders, ``build_pixel_decoder`` (pixel_decoder/fpn.py:21-33) and
+``build_transformer_decoder`` (maskformer_transformer_decoder.py:22-27) -- a registry lookup by the name in the
+config, then ``Cls(cfg, ...)`` -- are called with a config; they must return the bm2f classes.  A reference
+state_dict (the recorded names and shapes, filled by tests/golden/filler.py as the fixtures were made) loads strictly
+into each, and the outputs match the reference's golden fixtures on CPU (the oracle's MSDA / decoder restatements
+stand in for the HIP kernels here).
 
-Stand-ins for the absent detectron2 / fvcore mirror their behaviour where the check depends on it: the
-registry raises on a duplicate name like detectron2's Registry, and ``configurable`` routes a cfg through
-``from_config``.
+The stand-ins mirror the host's behaviour where the check depends on it: the registry raises on a duplicate name
+like detectron2's Registry, ``configurable`` routes a cfg through ``from_config``, and the host's registry module
+sits in ``sys.modules`` under the reference's module name, holding classes with the reference's names.
 """
 import functools
 import os
@@ -20,7 +24,6 @@ import sys
 import types
 from collections import namedtuple
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -97,25 +100,59 @@ def install_detectron2_standins():
     return ShapeSpec
 
 
-def main(ref_root):
+TD_MODULE = "mask2former.modeling.transformer_decoder.maskformer_transformer_decoder"
+
+
+def install_host_standins():
+    """The host's registry module under the reference's name, with same-name decoder / pixel-decoder classes
+    registered first, and its two builders.  Returns (module, build_pixel_decoder, build_transformer_decoder)."""
+    from detectron2.modeling import SEM_SEG_HEADS_REGISTRY
+    from detectron2.utils.registry import Registry
+    for pkg in ("mask2former", "mask2former.modeling", "mask2former.modeling.transformer_decoder"):
+        sys.modules[pkg] = types.ModuleType(pkg)
+    td = types.ModuleType(TD_MODULE)
+    td.TRANSFORMER_DECODER_REGISTRY = Registry("TRANSFORMER_MODULE")
+    sys.modules[TD_MODULE] = td
+
+    @td.TRANSFORMER_DECODER_REGISTRY.register()
+    class MultiScaleMaskedTransformerDecoder(nn.Module):     # the host's own class, registered first
+        pass
+
+    @SEM_SEG_HEADS_REGISTRY.register()
+    class MSDeformAttnPixelDecoder(nn.Module):
+        pass
+
+    def build_pixel_decoder(cfg, input_shape):
+        model = SEM_SEG_HEADS_REGISTRY.get(cfg.MODEL.SEM_SEG_HEAD.PIXEL_DECODER_NAME)(cfg, input_shape)
+        assert callable(getattr(model, "forward_features", None))
+        return model
+
+    def build_transformer_decoder(cfg, in_channels, mask_classification=True):
+        name = cfg.MODEL.MASK_FORMER.TRANSFORMER_DECODER_NAME
+        return td.TRANSFORMER_DECODER_REGISTRY.get(name)(cfg, in_channels, mask_classification)
+
+    td.HostDecoder, td.HostPixdec = MultiScaleMaskedTransformerDecoder, MSDeformAttnPixelDecoder
+    return td, build_pixel_decoder, build_transformer_decoder
+
+
+def reference_state_dict(which):
+    """The reference module's state_dict, re-created from its recorded names and shapes by the fixtures' filler."""
+    import json
+    from filler import fill_value
+    with open(os.path.join(HERE, "golden", "state_dict_shapes.json")) as f:
+        shapes = json.load(f)[which]
+    return {k: fill_value(k, shape).to(torch.float32) for k, shape in shapes.items()}
+
+
+def main():
     ShapeSpec = install_detectron2_standins()
     # INTEGRATION.md §1: bm2f's module stands in for the compiled MultiScaleDeformableAttention
     import bm2f_amd.msda
     sys.modules["MultiScaleDeformableAttention"] = bm2f_amd.msda
-    sys.path.insert(0, ref_root)
-    for pkg, rel in [("mask2former", "mask2former"), ("mask2former.modeling", "mask2former/modeling"),
-                     ("mask2former.modeling.pixel_decoder", "mask2former/modeling/pixel_decoder"),
-                     ("mask2former.modeling.transformer_decoder", "mask2former/modeling/transformer_decoder")]:
-        m = types.ModuleType(pkg)
-        m.__path__ = [os.path.join(ref_root, rel)]
-        sys.modules[pkg] = m
-    import importlib
-    td = importlib.import_module("mask2former.modeling.transformer_decoder.maskformer_transformer_decoder")
-    ref_dec = importlib.import_module("mask2former.modeling.transformer_decoder.mask2former_transformer_decoder")
-    ref_pd = importlib.import_module("mask2former.modeling.pixel_decoder.msdeformattn")
-    fpn = importlib.import_module("mask2former.modeling.pixel_decoder.fpn")
-    RefDecoder, RefPixdec = ref_dec.MultiScaleMaskedTransformerDecoder, ref_pd.MSDeformAttnPixelDecoder
-    assert td.TRANSFORMER_DECODER_REGISTRY.get("MultiScaleMaskedTransformerDecoder") is RefDecoder
+    td, build_pixel_decoder, build_transformer_decoder = install_host_standins()
+    from detectron2.modeling import SEM_SEG_HEADS_REGISTRY
+    assert td.TRANSFORMER_DECODER_REGISTRY.get("MultiScaleMaskedTransformerDecoder") is td.HostDecoder
+    assert SEM_SEG_HEADS_REGISTRY.get("MSDeformAttnPixelDecoder") is td.HostPixdec
 
     # the edited __init__.py files import bm2f's classes here (INTEGRATION.md §2)
     from bm2f_amd.pixel_decoder import MSDeformAttnPixelDecoder
@@ -125,30 +162,22 @@ def main(ref_root):
     cfg = default_cfg()
     shapes = {"res2": ShapeSpec(channels=256, stride=4), "res3": ShapeSpec(channels=512, stride=8),
               "res4": ShapeSpec(channels=1024, stride=16), "res5": ShapeSpec(channels=2048, stride=32)}
-    pd = fpn.build_pixel_decoder(cfg, shapes)                       # the reference's own builder
-    dec = td.build_transformer_decoder(cfg, 256, mask_classification=True)
+    pd = build_pixel_decoder(cfg, shapes)                           # the host's builder
+    dec = build_transformer_decoder(cfg, 256, mask_classification=True)
     assert type(pd) is MSDeformAttnPixelDecoder, type(pd)
     assert type(dec) is MultiScaleMaskedTransformerDecoder, type(dec)
 
-    from filler import fill_module
     from module_cases import oracle_msda, rel_err, run_decoder, run_pixdec
     from oracle.decoder_ref import torch_decoder_ops
     torch.manual_seed(0)
-    ref_m = fill_module(RefPixdec(shapes, transformer_dropout=0.0, transformer_nheads=8,
-                                  transformer_dim_feedforward=1024, transformer_enc_layers=6, conv_dim=256,
-                                  mask_dim=256, norm="GN", transformer_in_features=["res3", "res4", "res5"],
-                                  common_stride=4))
-    pd.load_state_dict(ref_m.state_dict(), strict=True)
+    pd.load_state_dict(reference_state_dict("pixdec"), strict=True)
     pd.train()
     with oracle_msda():
         g, feats, outs = run_pixdec(pd, torch.device("cpu"))
     for name, o in zip(["out_mask_features", "out_out0", "out_ms0", "out_ms1", "out_ms2"], outs):
         assert rel_err(o.detach(), g[name]) < 1e-4, name
 
-    ref_d = fill_module(RefDecoder(256, True, num_classes=133, hidden_dim=256, num_queries=100, nheads=8,
-                                   dim_feedforward=2048, dec_layers=9, pre_norm=False, mask_dim=256,
-                                   enforce_input_project=False))
-    dec.load_state_dict(ref_d.state_dict(), strict=True)
+    dec.load_state_dict(reference_state_dict("decoder"), strict=True)
     dec.train()
     with torch_decoder_ops():
         g, x, mf, logits, masks, _ = run_decoder(dec, torch.device("cpu"), "decoder.npz", False)
@@ -158,4 +187,4 @@ def main(ref_root):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else "/root/reference")
+    main()

@@ -40,8 +40,20 @@ def test_pixdec_forward_backward_cpu():
             assert rel_err(params[key[6:]].grad, g[key]) < 1e-4, key
 
 
+@pytest.fixture
+def generator_threads():
+    """The intra-op thread count the fixtures were generated with (gen_golden.py main).  The decoder runs free here
+    and its attention-mask bits must equal the fixture's: a mask logit within fp32 rounding of the threshold
+    (video_decoder_t5.npz holds one, in the last layer's mask) follows the fixture only when the CPU GEMMs sum in
+    the generator's order, which the thread count of the host running the test would otherwise change."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(8)
+    yield
+    torch.set_num_threads(n)
+
+
 @pytest.mark.parametrize("fixture", ["decoder.npz", "decoder_q200.npz", "video_decoder.npz", "video_decoder_t5.npz"])
-def test_decoder_forward_backward_cpu(fixture):
+def test_decoder_forward_backward_cpu(fixture, generator_threads):
     from module_cases import DECODER_CASES, run_decoder
     from oracle.decoder_ref import torch_decoder_ops, unpack_bits
     build, video = DECODER_CASES[fixture]

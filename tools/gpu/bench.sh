@@ -1,5 +1,7 @@
-# The bench line of the round (bench.py defaults: 10 timed steps, roofline_all, AMP fp16 / fp32 modes,
-# the CPU baseline) -> gpurun_out/bench.json.   gpurun --timeout 900 -- 'bash tools/gpu/bench.sh'
+# The full bench line (bench.py --full at its default steps: the timed steps, then roofline_all, the AMP bf16 /
+# fp32 modes, the achievable peaks, the op-level MSDA timing and the CPU baseline) -> OUTDIR/bench.json
+#   bash tools/gpu/bench.sh OUTDIR
 set -o pipefail
-cd "$GRAFT_REPO_ROOT" && mkdir -p gpurun_out && export TMPDIR=/tmp
-timeout -k 10 800 python -u bench.py 2> gpurun_out/bench.err | tee gpurun_out/bench.json
+out=$(mkdir -p "${1:?usage: bench.sh OUTDIR}" && cd "$1" && pwd) || exit 1
+cd "$(dirname "$0")/../.." && export TMPDIR=/tmp
+timeout -k 10 800 python -u bench.py --full 2> "$out/bench.err" | tee "$out/bench.json"

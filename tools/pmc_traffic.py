@@ -1,5 +1,5 @@
 """Turn a FETCH_SIZE pass and a WRITE_SIZE pass (rocprofv3 --pmc, separate runs) over the MSDA backward
-into profiles/msda_bwd_traffic.json, the HBM-traffic figure bench.py reports as roofline.traffic.
+into profiles/msda_bwd_traffic.json, the HBM-traffic figure bench.py --full reports as roofline.traffic.
 
 Units and gfx950 corrections follow /opt/skills/guides/MI355X_MICROARCH.md: both counters are KB;
 FETCH_SIZE is doubled (gfx950 tallies 128-B read requests at 64 B), WRITE_SIZE is taken as reported.
