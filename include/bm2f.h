@@ -487,6 +487,53 @@ int m2f_weaksup_lab(const float* images, int B, int Hp, int Wp, int stride, floa
 int m2f_color_similarity(const float* lab, const float* mask, int B, int h, int w, int dilation, float* sim,
                          void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Inference heads: the eval branch of MaskFormer.forward (maskformer_model.py:333-377) from the
+ * decoder's low-resolution mask logits.  Common arguments:
+ *   logits (B, Q, in_h, in_w) of `dtype` (M2F_F32 / M2F_F16 / M2F_BF16), converted to fp32 on load;
+ *          everything after is fp32, so for 16-bit logits the result is the reference's on
+ *          logits.float();
+ *   pad_h, pad_w  the padded batch size the reference upsamples to (:337-342);
+ *   sizes  (B, 4) int32 device table [Hc, Wc, Ho, Wo] per image: the crop (image size) and the
+ *          output size of sem_seg_postprocess (:355-357); the second bilinear resize is skipped
+ *          when (Ho, Wo) == (Hc, Wc).  Entries are clamped to pad_* / out_*;
+ *   out_h, out_w  row and column counts of the output buffers; rows and columns beyond an image's
+ *          (Ho, Wo) are left untouched.
+ * The full-resolution logit of a pixel is torch's upsample_bilinear2d (align_corners=False) formula
+ * evaluated literally, stage by stage (bm2f_amd/csrc/resize_device.h).  Q <= 256, else
+ * M2F_EUNSUPPORTED.  No entry point synchronises with the host.
+ * ------------------------------------------------------------------------------------------- */
+
+/* semantic_inference (:509-513): semseg (B, K, out_h, out_w) fp32 = sum_q probs[b, k, q] *
+ * sigmoid(logit_q), probs (B, K, Q) fp32 = softmax(pred_logits)[..., :-1] transposed; exact fp32 on
+ * the f32 MFMA.  With labels != NULL it writes labels (B, out_h, out_w) int16 = argmax_k (first
+ * maximum, as torch.argmax) instead and semseg is not touched (may be NULL).  K <= 256.  Non-finite
+ * logits are not handled as torch does: a pixel whose scores are all NaN gets label -1. */
+int m2f_infer_semantic(const void* logits, int dtype, const float* probs, const int32_t* sizes, int batch,
+                       int num_queries, int num_classes, int in_h, int in_w, int pad_h, int pad_w, int out_h,
+                       int out_w, float* semseg, int16_t* labels, void* stream);
+/* The pixel pass of panoptic_inference (:515-571).  keep_idx / keep_score (B, Q): the kept queries
+ * of each image in ascending order and their scores, num_keep (B,) int32 how many.  Outputs:
+ * winner (B, out_h, out_w) int16 = index into the kept list of argmax_k score_k * sigmoid(logit_k)
+ * (first maximum; -1 when num_keep == 0); inside (B, out_h, out_w) uint8 = the winner's own
+ * sigmoid >= 0.5; counters (B, Q, 3) int32 = [mask_area, original_area, intersection] per kept query
+ * (:544-548), zeroed here and counted with integer atomics (exact).  The caller runs the segment
+ * merging loop (:541-569) on the copied counters and maps winner through a segment-id table. */
+int m2f_infer_panoptic_pass(const void* logits, int dtype, const int32_t* keep_idx, const float* keep_score,
+                            const int32_t* num_keep, const int32_t* sizes, int batch, int num_queries, int in_h,
+                            int in_w, int pad_h, int pad_w, int out_h, int out_w, int16_t* winner, uint8_t* inside,
+                            int32_t* counters, void* stream);
+/* The pixel pass of instance_inference (:573-624).  sel_idx (B, max_sel) int32: distinct selected
+ * queries per image, num_sel (B,) how many.  masks (B, max_sel, out_h, out_w) uint8 = logit > 0
+ * (:615); sums (B, max_sel, 2) fp32 = [sum(sigmoid * binary), sum(binary)] (:621), reduced in a
+ * fixed order through partials (B, max_sel, num_tiles, 2) fp32 with
+ * num_tiles = ceil(out_h * out_w / 1024).  Slots >= num_sel get zero sums and untouched masks.
+ * out_h * out_w <= 2^24 (the pixel count is summed in fp32 and stays exact), else M2F_EUNSUPPORTED. */
+int m2f_infer_instance(const void* logits, int dtype, const int32_t* sel_idx, const int32_t* num_sel,
+                       const int32_t* sizes, int batch, int num_queries, int max_sel, int in_h, int in_w, int pad_h,
+                       int pad_w, int out_h, int out_w, int num_tiles, uint8_t* masks, float* partials, float* sums,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
