@@ -7,6 +7,9 @@ through the C ABI of ``include/bm2f.h``.
 from . import _native  # noqa: F401
 from .inference import (MaskFormerInference, instance_inference, panoptic_inference,  # noqa: F401
                         semantic_inference)
+from .video_criterion import (VideoHungarianMatcherProj, VideoHungarianMatcherProjPair,  # noqa: F401
+                              VideoSetCriterionProj, VideoSetCriterionProjSpatPair,
+                              VideoSetCriterionProjSpatPairTempPair)
 from .msda import MSDeformAttn, MSDeformAttnFunction, ms_deform_attn_backward, ms_deform_attn_forward  # noqa: F401
 
 __version__ = "0.1.0"

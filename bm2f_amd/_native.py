@@ -91,6 +91,10 @@ _SIGNATURES = {
     "m2f_threshold_bits": [_p, _i, _l, _f, _p, _p],
     "m2f_weaksup_lab": [_p, _i, _i, _i, _i, _p, _p],
     "m2f_color_similarity": [_p, _p, _i, _i, _i, _i, _p, _p],
+    "m2f_temporal_blocks": [_i],
+    "m2f_temporal_pairs_fwd": [_p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _i, _p, _p, _p],
+    "m2f_temporal_pairs_bwd": [_p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p],
+    "m2f_temporal_mine": [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p],
     "m2f_infer_semantic": [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p],
     "m2f_infer_panoptic_pass": [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p],
     "m2f_infer_instance": [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p],

@@ -2,8 +2,10 @@
 batched Hungarian matching, the pairwise-affinity cost / loss, neighbour-similarity bits and the GPU target
 preparation that replaces the reference's per-image host loop with skimage.
 
-Every op takes CUDA tensors and raises on anything else: there is no CPU path (the CPU restatement lives in
-``oracle/weaksup_ref.py`` and is test infrastructure only).
+Every image-criterion op takes CUDA tensors and raises on anything else: there is no CPU path (the CPU restatement
+lives in ``oracle/weaksup_ref.py`` and is test infrastructure only).  The temporal-pair ops of the video criterion
+(``csrc/video_pairs.hip``: packing, the temporal pairwise sum, pair mining) also evaluate their definition in plain
+torch on CPU tensors, like ``inference.py``.
 """
 from __future__ import annotations
 
@@ -220,6 +222,249 @@ class PairwiseSums(Function):
 
 def pairwise_sums(x, bits, t_row, box, box_row, dilation):
     return PairwiseSums.apply(x, bits, t_row, box, box_row, dilation)
+
+
+# --------------------------------------------------------------------------------------------------------
+# temporal pairs of the video criterion (mask2former_video/utils/weaksup_utils.py:64-165,
+# modeling/criterion_proj_spatpair_temppair.py:25-69, :269-334).  Unlike the ops above these also accept CPU
+# tensors and then evaluate the same definition in plain torch, so the video criterion's host logic is
+# testable without a GPU; on a HIP tensor a kernel error raises, there is no fall-back.
+# --------------------------------------------------------------------------------------------------------
+class MinedPairs:
+    """The temporal pairs of one clip in packed form: ``g`` (target), ``t`` (frame), ``p0`` / ``p1`` (linear
+    pixel y*w + x in frame t / t+1), all (P,) int32 on the features' device and ordered by (g, t, current
+    pixel row-major); ``counts`` (G, T-1) host ints = pairs per (target, frame pair)."""
+
+    def __init__(self, g, t, p0, p1, counts, T, h, w):
+        self.g, self.t, self.p0, self.p1 = g, t, p0, p1
+        self.counts = counts
+        self.T, self.h, self.w = int(T), int(h), int(w)
+
+    def __len__(self):
+        return len(self.counts)
+
+    def to_lists(self):
+        """The reference's nested ``[[(curr (k, 2), next (k, 2))] * (T-1)] * G`` int32 XY lists
+        (video_maskformer_model.py:523-558); no host synchronisation."""
+        w = self.w
+        curr = torch.stack([self.p0 % w, self.p0 // w], 1)
+        nxt = torch.stack([self.p1 % w, self.p1 // w], 1)
+        sizes = [int(c) for row in self.counts for c in row]
+        cs, ns = curr.split(sizes), nxt.split(sizes)
+        n = self.T - 1
+        return [[(cs[g * n + t], ns[g * n + t]) for t in range(n)] for g in range(len(self.counts))]
+
+
+def _from_host(a, device):
+    t = torch.from_numpy(a)
+    return t.pin_memory().to(device, non_blocking=True) if torch.device(device).type == "cuda" else t
+
+
+def _argmin_sqdist(a, b):
+    """First arg-min over rows of b of sum_d (a - b)^2, rows of a in chunks (no full distance matrix)."""
+    step = max(1, (1 << 22) // max(1, b.shape[0] * a.shape[1]))
+    out = [((a[i:i + step, None] - b[None]) ** 2).sum(-1).argmin(1) for i in range(0, a.shape[0], step)]
+    return torch.cat(out)
+
+
+def temporal_pairs(feats: torch.Tensor, boxes: torch.Tensor, k: int = 1) -> MinedPairs:
+    """Temporal pair mining for all instances and frame pairs of one clip (``get_instance_temporal_pairs``
+    looped as in video_maskformer_model.py:523-558).
+
+    feats (T, D, h, w) fp32; boxes (G, T, 4) integer XYXY, sliced half-open (``[y0:y1, x0:x1]``, clipped to
+    the frame as slicing does).  For every instance and every t where both boxes have positive area, each
+    pixel of the frame-t box (row-major) is paired with the frame-(t+1) box pixel at the smallest L2 feature
+    distance; k == 1 on a HIP tensor is one launch of ``m2f_temporal_mine`` over all segments (distances as
+    sums of (a-b)^2 in fp32, first minimum).  k > 1 is the reference's cdist().half().topk(k) in torch.
+    The boxes are read on the host once."""
+    if feats.dim() != 4 or boxes.dim() != 3 or boxes.shape[-1] != 4 or boxes.shape[1] != feats.shape[0]:
+        raise ValueError("feats must be (T, D, h, w) and boxes (G, T, 4)")
+    if boxes.is_floating_point() or k < 1:
+        raise ValueError("boxes must be integer XYXY and k >= 1")
+    import numpy as np
+    T, D, h, w = feats.shape
+    dev = feats.device
+    bx = boxes.detach().cpu().numpy().astype(np.int64)
+    if (bx < 0).any():
+        raise ValueError("boxes must be non-negative pixel coordinates")
+    G = bx.shape[0]
+    bx = np.minimum(bx, np.array([w, h, w, h]))
+    pos = (bx[..., 2] > bx[..., 0]) & (bx[..., 3] > bx[..., 1])
+    counts = np.zeros((G, max(T - 1, 0)), np.int64)
+    segs, blocks, g_l, t_l, p0_l = [], [], [], [], []
+    off = 0
+    for g in range(G):
+        for t in range(T - 1):
+            if not (pos[g, t] and pos[g, t + 1]):
+                continue
+            cx0, cy0, cx1, cy1 = bx[g, t]
+            nx0, ny0, nx1, ny1 = bx[g, t + 1]
+            cw, nw = cx1 - cx0, nx1 - nx0
+            nc, nn = cw * (cy1 - cy0), nw * (ny1 - ny0)
+            kk = min(k, nn)
+            j = np.arange(nc)
+            blocks += [(len(segs), c) for c in range((nc + 63) // 64)]
+            segs.append((t, cx0, cy0, cw, nc, nx0, ny0, nw, nn, off))
+            p0_l.append(np.repeat((cy0 + j // cw) * w + cx0 + j % cw, kk))
+            g_l.append(np.full(nc * kk, g))
+            t_l.append(np.full(nc * kk, t))
+            counts[g, t] = nc * kk
+            off += nc * kk
+    cat = lambda parts: np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)  # noqa: E731
+    g_d, t_d, p0_d = (_from_host(cat(x), dev) for x in (g_l, t_l, p0_l))
+    x = feats.float().contiguous()
+    if k == 1 and x.is_cuda:
+        p1 = torch.zeros(off, dtype=torch.int32, device=dev)
+        if segs:
+            seg_d = _from_host(np.asarray(segs, np.int32), dev)
+            blk_d = _from_host(np.asarray(blocks, np.int32), dev)
+            _native.call("m2f_temporal_mine", x.data_ptr(), T, D, h, w, seg_d.data_ptr(), len(segs), blk_d.data_ptr(),
+                         len(blocks), p1.data_ptr(), off, _stream(x))
+    else:
+        parts = []
+        for (t, cx0, cy0, cw, nc, nx0, ny0, nw, nn, _) in segs:
+            a = x[t, :, cy0:cy0 + nc // cw, cx0:cx0 + cw].flatten(1).t()
+            b = x[t + 1, :, ny0:ny0 + nn // nw, nx0:nx0 + nw].flatten(1).t()
+            if k == 1:
+                j = _argmin_sqdist(a, b)
+            else:
+                j = (-torch.cdist(a, b, p=2).half()).topk(k=min(k, nn), dim=1)[1].flatten()
+            parts.append(((ny0 + j // nw) * w + nx0 + j % nw).to(torch.int32))
+        p1 = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int32, device=dev)
+    return MinedPairs(g_d, t_d, p0_d, p1, counts.tolist(), T, h, w)
+
+
+class PackedPairs:
+    """All temporal pairs of a batch of clips, packed once per criterion call: ``row`` (flat target row over
+    the batch, -1 for a pair with an out-of-frame coordinate), ``t``, ``p0``, ``p1`` (P,) int32, and the
+    2P endpoints sorted stably by ``ep_key`` = (row * T + frame) * H*W + pixel with ``ep_code`` = 2 * pair
+    + side.  Runs of equal keys are the segments the backward kernel owns one thread each.  ``bad`` is a
+    device bool: some pair was out of frame (checked with the matcher status, one sync per call)."""
+
+    def __init__(self, row, t, p0, p1, ep_key, ep_code, n_targets, T, H, W, bad):
+        self.row, self.t, self.p0, self.p1 = row, t, p0, p1
+        self.ep_key, self.ep_code = ep_key, ep_code
+        self.P = int(row.shape[0])
+        self.n_targets, self.T, self.H, self.W = int(n_targets), int(T), int(H), int(W)
+        self.bad = bad
+
+
+def pack_temporal_pairs(per_clip, T: int, H: int, W: int, device) -> PackedPairs:
+    """per_clip[b]: a :class:`MinedPairs` or the reference's nested lists (XY coordinates) of clip b's
+    targets.  Sizes come from tensor shapes, so nothing synchronises."""
+    import numpy as np
+    rows, ts, c0, c1 = [], [], [], []
+    off = 0
+    for clip in per_clip:
+        if isinstance(clip, MinedPairs):
+            if (clip.T, clip.h, clip.w) != (T, H, W):
+                raise ValueError("temporal pairs were mined at another clip size")
+            if clip.g.numel():
+                rows.append(clip.g.to(device).long() + off)
+                ts.append(clip.t.to(device).long())
+                c0.append(clip.p0.to(device).long())
+                c1.append(clip.p1.to(device).long())
+        else:
+            r_h, t_h = [], []
+            for g, per_frame in enumerate(clip):
+                if len(per_frame) != T - 1:
+                    raise ValueError("temporal_pairs needs T - 1 entries per target")
+                for t, (cur, nxt) in enumerate(per_frame):
+                    if cur.shape != nxt.shape:
+                        raise ValueError("current / next pair coordinates differ in shape")
+                    if cur.shape[0] == 0:
+                        continue
+                    r_h.append(np.full(cur.shape[0], off + g))
+                    t_h.append(np.full(cur.shape[0], t))
+                    cur, nxt = cur.to(device).long(), nxt.to(device).long()
+                    ok = (cur[:, 0] >= 0) & (cur[:, 0] < W) & (cur[:, 1] >= 0) & (cur[:, 1] < H) & \
+                         (nxt[:, 0] >= 0) & (nxt[:, 0] < W) & (nxt[:, 1] >= 0) & (nxt[:, 1] < H)
+                    c0.append(torch.where(ok, cur[:, 1] * W + cur[:, 0], -1))
+                    c1.append(torch.where(ok, nxt[:, 1] * W + nxt[:, 0], -1))
+            if r_h:
+                rows.append(_from_host(np.concatenate(r_h), device))
+                ts.append(_from_host(np.concatenate(t_h), device))
+        off += len(clip)
+    if not rows:
+        e32 = torch.zeros(0, dtype=torch.int32, device=device)
+        return PackedPairs(e32, e32, e32, e32, torch.zeros(0, dtype=torch.int64, device=device), e32, off, T, H, W,
+                           torch.zeros((), dtype=torch.bool, device=device))
+    row, t, p0, p1 = (torch.cat(x) for x in (rows, ts, c0, c1))
+    HW = H * W
+    ok = (p0 >= 0) & (p0 < HW) & (p1 >= 0) & (p1 < HW) & (t >= 0) & (t < T - 1)
+    row = torch.where(ok, row, -1)
+    t, p0, p1 = (torch.where(ok, v, 0) for v in (t, p0, p1))
+    keys = torch.stack([torch.where(ok, (row * T + t) * HW + p0, -1),
+                        torch.where(ok, (row * T + t + 1) * HW + p1, -1)], 1).view(-1)
+    ep_key, order = torch.sort(keys, stable=True)
+    i32 = lambda v: v.to(torch.int32).contiguous()  # noqa: E731
+    return PackedPairs(i32(row), i32(t), i32(p0), i32(p1), ep_key.contiguous(), i32(order), off, T, H, W,
+                       (~ok).any())
+
+
+def _pair_term_torch(a, b):
+    """calculate_temp_similarities (criterion_proj_spatpair_temppair.py:56-69), the reference's own form."""
+    import torch.nn.functional as F
+    fg = F.logsigmoid(a) + F.logsigmoid(b)
+    bg = F.logsigmoid(-a) + F.logsigmoid(-b)
+    m = torch.max(fg, bg)
+    return -(torch.log(torch.exp(fg - m) + torch.exp(bg - m)) + m)
+
+
+class TemporalPairSum(Function):
+    """(sum of s over the live pairs, their count) for matched masks src (N, T, H, W); differentiable in
+    src.  The backward pass writes each touched pixel once, in a fixed order (bitwise repeatable)."""
+
+    @staticmethod
+    def forward(ctx, src, row_of_target, pk):
+        N, T, H, W = src.shape
+        nb = _native.load().m2f_temporal_blocks(pk.P)
+        part_sum = torch.empty(nb, dtype=torch.float32, device=src.device)
+        part_cnt = torch.empty(nb, dtype=torch.int32, device=src.device)
+        _native.call("m2f_temporal_pairs_fwd", src.data_ptr(), N, T, H, W, row_of_target.data_ptr(), pk.n_targets,
+                     pk.row.data_ptr(), pk.t.data_ptr(), pk.p0.data_ptr(), pk.p1.data_ptr(), pk.P,
+                     part_sum.data_ptr(), part_cnt.data_ptr(), _stream(src))
+        ctx.save_for_backward(src, row_of_target)
+        ctx.pk = pk
+        total, count = part_sum.sum(), part_cnt.sum()
+        ctx.mark_non_differentiable(count)
+        return total, count
+
+    @staticmethod
+    def backward(ctx, g_total, g_count):
+        src, row_of_target = ctx.saved_tensors
+        pk = ctx.pk
+        N, T, H, W = src.shape
+        grad = torch.zeros_like(src)
+        g = g_total.float().reshape(1).contiguous()
+        _native.call("m2f_temporal_pairs_bwd", src.data_ptr(), N, T, H, W, row_of_target.data_ptr(), pk.n_targets,
+                     pk.row.data_ptr(), pk.t.data_ptr(), pk.p0.data_ptr(), pk.p1.data_ptr(), pk.P,
+                     pk.ep_key.data_ptr(), pk.ep_code.data_ptr(), g.data_ptr(), grad.data_ptr(), _stream(src))
+        return grad, None, None
+
+
+def temporal_pair_sum(src: torch.Tensor, row_of_target: torch.Tensor, pk: PackedPairs):
+    """Sum of the temporal pair terms of matched masks src (N, T, H, W) fp32 and the number of live pairs
+    (an int tensor on src's device; no host synchronisation).  ``row_of_target`` (pk.n_targets,) int32 maps
+    a flat target row to its row of src or -1; pairs of unmatched targets are dead."""
+    if src.dim() != 4 or src.dtype != torch.float32 or (src.shape[1:] != (pk.T, pk.H, pk.W) and pk.P):
+        raise ValueError("src must be fp32 (N, T, H, W) of the packed pairs' clip size")
+    if row_of_target.dtype != torch.int32 or row_of_target.numel() != pk.n_targets:
+        raise ValueError("row_of_target must be int32 with one entry per target")
+    if src.is_cuda:
+        _need_cuda(row_of_target, pk.row, pk.ep_key)
+        return TemporalPairSum.apply(src.contiguous(), row_of_target.contiguous(), pk)
+    N = src.shape[0]
+    if N == 0 or pk.P == 0:
+        return src.sum() * 0.0, torch.zeros((), dtype=torch.int64)
+    HW = pk.H * pk.W
+    n = torch.where(pk.row >= 0, row_of_target.long()[pk.row.clamp(min=0).long()], -1)
+    live = n >= 0
+    n = n[live]
+    t, p0, p1 = pk.t.long()[live], pk.p0.long()[live], pk.p1.long()[live]
+    flat = src.reshape(N, -1)
+    s = _pair_term_torch(flat[n, t * HW + p0], flat[n, (t + 1) * HW + p1])
+    return s.sum(), live.sum()
 
 
 # --------------------------------------------------------------------------------------------------------

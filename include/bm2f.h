@@ -488,6 +488,42 @@ int m2f_color_similarity(const float* lab, const float* mask, int B, int h, int 
                          void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Box-supervised video criterion (mask2former_video/modeling/criterion_proj_spatpair_temppair.py):
+ * temporal pairwise loss and temporal pair mining.  Pairs are packed as four int32 arrays of length P:
+ * pair_row (flat target row, < 0: dead pair), pair_t (frame t in [0, T-1)), pair_p0 / pair_p1 (linear
+ * pixel y*W + x in frame t / t+1).  row_of_target (n_targets,) int32 maps a target row to its matched
+ * row n of src (N, T, H, W) fp32 contiguous, or -1.  A pair with any index out of range, or whose
+ * target is unmatched, is dead: it adds nothing and is not counted.  H*W < 2^31.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Number of per-block partials the forward writes for P pairs. */
+int m2f_temporal_blocks(int P);
+/* part_sum[k] = sum over block k's live pairs of s = -log(sig(a)sig(b) + sig(-a)sig(-b)) (log-space
+ * form of m2f_pairwise_rows), a = src[n, t, p0], b = src[n, t+1, p1]; part_cnt[k] = its live pairs.
+ * The caller sums the m2f_temporal_blocks(P) partials (fixed order; no host synchronisation). */
+int m2f_temporal_pairs_fwd(const float* src, int N, int T, int H, int W, const int* row_of_target, int n_targets,
+                           const int* pair_row, const int* pair_t, const int* pair_p0, const int* pair_p1, int P,
+                           float* part_sum, int* part_cnt, void* stream);
+/* grad (N, T, H, W), zeroed by the caller, gets grad_scale[0] * d(sum of s)/d src.  ep_key / ep_code
+ * (2P): the endpoints of all pairs sorted (stably) by ep_key = (pair_row * T + frame) * H*W + pixel
+ * (-1 for a dead pair), ep_code = 2 * pair + side (side 1: the frame t+1 endpoint).  The thread on
+ * the first endpoint of each run of equal keys sums the run in stored order and writes the pixel
+ * once: no atomics, bitwise repeatable. */
+int m2f_temporal_pairs_bwd(const float* src, int N, int T, int H, int W, const int* row_of_target, int n_targets,
+                           const int* pair_row, const int* pair_t, const int* pair_p0, const int* pair_p1, int P,
+                           const int64_t* ep_key, const int* ep_code, const float* grad_scale, float* grad,
+                           void* stream);
+/* Temporal pair mining (utils/weaksup_utils.py:64-165 with topk_match = 1) over all (instance, frame
+ * pair) segments in one launch.  feats (T, D, h, w) fp32.  segs (n_segs, 10) int32: t, cx0, cy0, cw,
+ * nc, nx0, ny0, nw, nn, out_off -- the frame-t box (origin, width, pixel count), the frame-(t+1) box
+ * and the segment's offset in out_p1; boxes lie inside the frame.  blocks (n_blocks, 2) int32:
+ * (segment, 64-pixel tile of its current box), one workgroup each.  out_p1[out_off + j] = linear
+ * pixel y*w + x of the next-box pixel at the smallest squared L2 feature distance (summed as
+ * (a-b)^2 in fp32; first minimum in row-major order) from current-box pixel j (row-major). */
+int m2f_temporal_mine(const float* feats, int T, int D, int h, int w, const int* segs, int n_segs,
+                      const int* blocks, int n_blocks, int* out_p1, int n_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Inference heads: the eval branch of MaskFormer.forward (maskformer_model.py:333-377) from the
  * decoder's low-resolution mask logits.  Common arguments:
  *   logits (B, Q, in_h, in_w) of `dtype` (M2F_F32 / M2F_F16 / M2F_BF16), converted to fp32 on load;
