@@ -7,6 +7,7 @@ through the C ABI of ``include/bm2f.h``.
 from . import _native  # noqa: F401
 from .inference import (MaskFormerInference, instance_inference, panoptic_inference,  # noqa: F401
                         semantic_inference)
+from .mask_criterion import HungarianMatcher, SetCriterion, VideoHungarianMatcher, VideoSetCriterion  # noqa: F401
 from .video_criterion import (VideoHungarianMatcherProj, VideoHungarianMatcherProjPair,  # noqa: F401
                               VideoSetCriterionProj, VideoSetCriterionProjSpatPair,
                               VideoSetCriterionProjSpatPairTempPair)

@@ -95,6 +95,12 @@ _SIGNATURES = {
     "m2f_temporal_pairs_fwd": [_p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _i, _p, _p, _p],
     "m2f_temporal_pairs_bwd": [_p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p],
     "m2f_temporal_mine": [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p],
+    "m2f_point_match_workspace": [_i, _i, _i, _i, _i, _p],
+    "m2f_point_match_cost": [_p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _f, _f, _f, _p, _l, _p, _p],
+    "m2f_point_uncertainty": [_p, _i, _l, _i, _i, _p, _i, _p, _i, _p, _p],
+    "m2f_point_loss_chunks": [_i],
+    "m2f_point_loss_fwd": [_p, _i, _l, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p],
+    "m2f_point_loss_bwd": [_p, _i, _l, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p],
     "m2f_infer_semantic": [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p],
     "m2f_infer_panoptic_pass": [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p],
     "m2f_infer_instance": [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p],

@@ -1,0 +1,500 @@
+"""Mask-supervised Hungarian matcher and set criterion (``SUP_TYPE: "mask"``) on fused HIP point sampling.
+
+Drop-ins for the reference's ``HungarianMatcher`` (mask2former/modeling/matcher.py:479-597), ``SetCriterion``
+(modeling/criterion.py:775-955), ``VideoHungarianMatcher`` (mask2former_video/modeling/matcher.py:503-590) and
+``VideoSetCriterion`` (mask2former_video/modeling/criterion.py:144-310): same constructor arguments, the
+``empty_weight`` buffer, ``__repr__``, ``forward(outputs, targets)`` contracts and loss keys (``loss_ce``,
+``loss_mask``, ``loss_dice`` and the ``_i`` aux copies).  Inputs as in the reference: ``pred_logits`` (B, Q, C+1),
+``pred_masks`` (B, Q, H, W) or (B, Q, T, H, W) in fp32 / fp16 / bf16 (evaluated in fp32); target dicts with
+``labels`` and ``masks`` (G, Ht, Wt) / (G, T, Ht, Wt) (bool, uint8 or float, at their own resolution), and
+``box_masks_full`` for ``mask_target_type="box_mask"``.
+
+Semantics (``point_sample(x, u) = grid_sample(x, 2u - 1, bilinear, zeros, align_corners=False)``):
+
+* matcher: one set of ``num_points`` coordinates per image, shared by its Q predictions and G targets (and, for
+  video, by all T frames); ``cost_mask = (sum_k softplus(x_qk) - sum_k x_qk t_gk) / K`` (the reference's
+  ``pos . t + neg . (1 - t)``: softplus(-x) - softplus(x) = -x), ``cost_dice = 1 - (2 sum sig(x) t + 1) /
+  (sum sig(x) + sum t + 1)``, class cost ``-softmax[:, labels]``; video sums and the divisor run over T K;
+* criterion, per head: ``int(num_points * oversample_ratio)`` uniform points per matched mask (video: per matched
+  (mask, frame) row) -> uncertainty ``-|x|`` -> the ``int(importance_sample_ratio * num_points)`` most uncertain
+  -> plus ``num_points`` minus that fresh uniform points -> ``loss_mask = sum_rows mean_k BCE / num_masks``,
+  ``loss_dice = sum_rows (1 - (2 sum sig t + 1) / (sum sig + sum t + 1)) / num_masks`` (detectron2's
+  ``get_uncertain_point_coords_with_randomness``);
+* the image criterion normalises target coordinates over the batch's padded size (``nested_tensor_from_tensor_list``
+  pads bottom / right with zeros); the matcher uses each image's own size.  The pad is never materialised.
+
+Where the work runs on a HIP device (csrc/point_sample.hip): the matching cost of all images of a head is one
+``m2f_point_match_cost`` call (no (B, Q, K) tensor, bitwise repeatable) feeding one ``m2f_lsap_batched`` launch;
+the oversampling pass is ``m2f_point_uncertainty`` + ``torch.topk``; the losses are the ``m2f_point_loss_fwd`` /
+``_bwd`` pair, which reads predictions through a plane index table and targets in place through a pointer table
+(no gathered ``pred_masks[src_idx]``, no float copy of the targets) and scatters the gradient with fp32 atomics into
+one dense buffer per head.  ``num_masks`` stays a device scalar under torch.distributed; matcher status is checked
+with one sync per criterion call (``check_matching = False`` skips it).  Indices are int64 tensors on the masks'
+device.
+
+Randomness: every module has a settable ``point_source(kind, shape, device) -> float32 tensor in [0, 1)`` (default
+``torch.rand`` on the masks' device), called exactly once per kind per head, in head order (main, aux 0, ...):
+``"match"`` (B, K, 2), ``"oversample"`` (N, K * ratio, 2), ``"random"`` (N, K_random, 2; not called when that is 0).
+A criterion passes its own source to its matcher unless the matcher has one set.  The distribution is the
+reference's; the random stream is not.
+
+On CPU tensors the same classes evaluate the same definition in plain torch (``F.grid_sample``, ``torch.topk``,
+scipy).  That is not a fall-back: on a HIP tensor a kernel error raises.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+from torch import nn
+from torch.autograd import Function
+
+from . import _native
+from . import weaksup as ws
+from .criterion import _dist_world
+
+_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def _rand_source(kind, shape, device):
+    return torch.rand(shape, device=device)
+
+
+def point_sample(x, u):
+    """x (N, C, H, W), u (N, P, 2) in [0, 1] -> (N, C, P) (detectron2's point_sample, align_corners=False)."""
+    return F.grid_sample(x, 2.0 * u[:, :, None] - 1.0, mode="bilinear", padding_mode="zeros",
+                         align_corners=False).squeeze(3)
+
+
+def _logit_tensor(masks):
+    """The masks in a dtype the kernels read (fp32 / fp16 / bf16), contiguous."""
+    if masks.dtype not in _DTYPES:
+        masks = masks.float()
+    return masks.contiguous()
+
+
+class MaskTargets:
+    """Per-call target tensors shared by the matcher and the mask loss of all decoder heads.  The masks are kept as
+    they are (bool viewed as uint8, uint8 or fp32; anything else is converted to fp32 once) and addressed by the
+    kernels through pointer tables built here without a host synchronisation."""
+
+    def __init__(self, targets, device, video):
+        self.device = torch.device(device)
+        self.cuda = self.device.type == "cuda"
+        self.video = video
+        self.B = len(targets)
+        self.G = [int(t["labels"].shape[0]) for t in targets]
+        self.Gm = max(self.G) if self.G else 0
+        self.offsets = np.concatenate([[0], np.cumsum(self.G)]).astype(np.int64).tolist()
+        self.labels = [t["labels"].to(device) for t in targets]
+        self._targets = targets
+        self._planes = {}
+        self._labels_padded = None
+
+    def labels_padded(self):
+        if self._labels_padded is None:
+            lab = torch.zeros((self.B, self.Gm), dtype=torch.int64, device=self.device)
+            for b, l in enumerate(self.labels):
+                if self.G[b]:
+                    lab[b, :self.G[b]] = l
+            self._labels_padded = lab
+        return self._labels_padded
+
+    def planes(self, key="masks"):
+        """dict: ``list`` per-image planes (G, [T,] Ht, Wt), ``code`` 0 uint8 / 1 fp32, ``sizes`` (Ht, Wt) per
+        image, ``pad`` the batch maximum, and on a HIP device ``match`` (B, 4) int64 [pointer, G, Ht, Wt] and
+        ``rows`` (B, 4) int64 [pointer, plane bytes, Ht, Wt]."""
+        hit = self._planes.get(key)
+        if hit is not None:
+            return hit
+        raw = [t[key].to(self.device) for t in self._targets]
+        nd = 4 if self.video else 3
+        for b, m in enumerate(raw):
+            if m.dim() != nd or m.shape[0] != self.G[b]:
+                raise ValueError(f"targets[{b}][{key!r}] must be (G, {'T, ' if self.video else ''}H, W) with one "
+                                 "mask per label")
+        as_u8 = all(m.dtype in (torch.bool, torch.uint8) for m in raw)
+        if as_u8:
+            lst = [(m.view(torch.uint8) if m.dtype == torch.bool else m).contiguous() for m in raw]
+        else:
+            lst = [m.to(torch.float32).contiguous() for m in raw]
+        sizes = [(int(m.shape[-2]), int(m.shape[-1])) for m in lst]
+        out = {"list": lst, "code": 0 if as_u8 else 1, "sizes": sizes,
+               "pad": (max((s[0] for s in sizes), default=0), max((s[1] for s in sizes), default=0))}
+        if self.cuda:
+            item = 1 if as_u8 else 4
+            # an image without targets has no storage to point at: null pointer, skipped by the kernels
+            ptr = [m.data_ptr() if m.numel() else 0 for m in lst]
+            out["match"] = ws.h2d([v for b in range(self.B) for v in (ptr[b], self.G[b], *sizes[b])], self.device,
+                                  torch.int64).view(self.B, 4)
+            out["rows"] = ws.h2d([v for b in range(self.B) for v in (ptr[b], sizes[b][0] * sizes[b][1] * item,
+                                                                      *sizes[b])], self.device,
+                                 torch.int64).view(self.B, 4)
+        self._planes[key] = out
+        return out
+
+
+# ------------------------------------------------------------------------------------------------------------
+# kernels
+# ------------------------------------------------------------------------------------------------------------
+def match_cost(masks, coords, tgt_table, tgt_code, Gm, cost_class=None, w_class=0.0, w_mask=1.0, w_dice=1.0):
+    """``m2f_point_match_cost``: masks (B, Q, H, W) or (B, Q, T, H, W), coords (B, K, 2) fp32, tgt_table (B, 4)
+    int64 -> (B, Q, Gm) fp32 weighted cost.  The caller keeps the target tensors alive."""
+    ws._need_cuda(masks, coords, tgt_table, cost_class)
+    x = _logit_tensor(masks)
+    B, Q = x.shape[:2]
+    T = x.shape[2] if x.dim() == 5 else 1
+    H, W = x.shape[-2:]
+    K = coords.shape[1]
+    c = coords.to(torch.float32).contiguous()
+    if c.shape != (B, K, 2) or tgt_table.shape != (B, 4) or tgt_table.dtype != torch.int64:
+        raise ValueError("coords must be (B, K, 2) and the target table (B, 4) int64")
+    cc = None
+    if cost_class is not None:
+        cc = cost_class.to(torch.float32).contiguous()
+        if cc.shape != (B, Q, Gm):
+            raise ValueError("cost_class must be (B, Q, Gm)")
+    n = ctypes.c_int64()
+    _native.call("m2f_point_match_workspace", B, T, Q, Gm, K, ctypes.byref(n))
+    work = torch.empty(max(n.value, 1), dtype=torch.float32, device=x.device)
+    cost = torch.empty((B, Q, Gm), dtype=torch.float32, device=x.device)
+    _native.call("m2f_point_match_cost", x.data_ptr(), _DTYPES[x.dtype], B, Q, T, H, W, c.data_ptr(), K,
+                 tgt_table.contiguous().data_ptr(), tgt_code, Gm, ws._ptr(cc), ctypes.c_float(w_class),
+                 ctypes.c_float(w_mask), ctypes.c_float(w_dice), work.data_ptr(), ctypes.c_int64(n.value),
+                 cost.data_ptr(), ws._stream(x))
+    return cost
+
+
+def point_uncertainty(masks, plane, coords):
+    """``-|point_sample(masks.view(-1, H, W)[plane[r]], coords[r])|``: plane (R,) int64, coords (R, P, 2) ->
+    (R, P) fp32."""
+    ws._need_cuda(masks, plane, coords)
+    x = _logit_tensor(masks)
+    H, W = x.shape[-2:]
+    R, P = coords.shape[:2]
+    c = coords.to(torch.float32).contiguous()
+    out = torch.empty((R, P), dtype=torch.float32, device=x.device)
+    _native.call("m2f_point_uncertainty", x.data_ptr(), _DTYPES[x.dtype], ctypes.c_int64(x.numel() // (H * W)), H, W,
+                 plane.contiguous().data_ptr(), R, c.data_ptr(), P, out.data_ptr(), ws._stream(x))
+    return out
+
+
+class PointLossSums(Function):
+    """Per row r: sum_k BCE(x, t), sum sig(x) t, sum sig(x), sum t at the row's K points; x sampled from plane
+    ``plane[r]`` of masks, t from the row's target (tgt_rows (R, 5) int64: pointer, Ht, Wt, Hn, Wn).  Differentiable
+    in masks: the backward pass re-samples (only the tables and coordinates are saved) and scatters with fp32
+    atomics into one dense gradient."""
+
+    @staticmethod
+    def forward(ctx, masks, plane, coords, tgt_rows, tgt_code, keep):
+        H, W = masks.shape[-2:]
+        R, K = coords.shape[:2]
+        chunks = _native.load().m2f_point_loss_chunks(K)
+        part = torch.empty((R, max(chunks, 1), 4), dtype=torch.float32, device=masks.device)
+        n_planes = masks.numel() // (H * W)
+        _native.call("m2f_point_loss_fwd", masks.data_ptr(), _DTYPES[masks.dtype], ctypes.c_int64(n_planes), H, W,
+                     plane.data_ptr(), R, coords.data_ptr(), K, tgt_rows.data_ptr(), tgt_code, part.data_ptr(),
+                     ws._stream(masks))
+        ctx.save_for_backward(masks, plane, coords, tgt_rows)
+        ctx.tgt_code = tgt_code
+        ctx.keep = keep                      # the target tensors the pointer table refers to
+        sums = part.sum(1)
+        bce, inter, sig, tsum = sums.unbind(1)
+        ctx.mark_non_differentiable(tsum)
+        return bce, inter, sig, tsum
+
+    @staticmethod
+    def backward(ctx, g_bce, g_inter, g_sig, g_t):
+        masks, plane, coords, tgt_rows = ctx.saved_tensors
+        H, W = masks.shape[-2:]
+        R, K = coords.shape[:2]
+        g = torch.stack([g_bce, g_inter, g_sig], 1).to(torch.float32).contiguous()
+        grad = torch.zeros(masks.shape, dtype=torch.float32, device=masks.device)
+        _native.call("m2f_point_loss_bwd", masks.data_ptr(), _DTYPES[masks.dtype], ctypes.c_int64(grad.numel() // (H * W)),
+                     H, W, plane.data_ptr(), R, coords.data_ptr(), K, tgt_rows.data_ptr(), ctx.tgt_code, g.data_ptr(),
+                     grad.data_ptr(), ws._stream(masks))
+        return grad.to(masks.dtype), None, None, None, None, None
+
+
+def point_loss_sums(masks, plane, coords, tgt_rows, tgt_code, keep=None):
+    ws._need_cuda(masks, plane, coords, tgt_rows)
+    if tgt_rows.dtype != torch.int64 or tgt_rows.shape != (coords.shape[0], 5) or plane.dtype != torch.int64:
+        raise ValueError("plane must be (R,) int64 and the target table (R, 5) int64")
+    return PointLossSums.apply(_logit_tensor(masks), plane.contiguous(), coords.to(torch.float32).contiguous(),
+                               tgt_rows.contiguous(), tgt_code, keep)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# matchers
+# ------------------------------------------------------------------------------------------------------------
+class HungarianMatcher(nn.Module):
+    """Reference: mask2former/modeling/matcher.py:479-597 (same arguments; no buffers)."""
+
+    _video = False
+
+    def __init__(self, cost_class: float = 1, cost_mask: float = 1, cost_dice: float = 1, num_points: int = 0):
+        super().__init__()
+        self.cost_class = cost_class
+        self.cost_mask = cost_mask
+        self.cost_dice = cost_dice
+        assert cost_class != 0 or cost_mask != 0 or cost_dice != 0, "all costs cant be 0"
+        self.num_points = num_points
+        self.point_source = None     # None: the caller's (a criterion's) source, else torch.rand
+        self.last_status = None
+
+    @torch.no_grad()
+    def cost_matrix(self, outputs, tg: MaskTargets, coords) -> torch.Tensor:
+        """(B, Q, Gm) fp32 matching cost of every image / clip at coords (B, K, 2) (columns >= G_b: padding)."""
+        logits, masks = outputs["pred_logits"], outputs["pred_masks"]
+        B, Q = logits.shape[:2]
+        Gm = tg.Gm
+        pl = tg.planes("masks")
+        prob = logits.float().softmax(-1)
+        c_class = -torch.gather(prob, 2, tg.labels_padded()[:, None, :].expand(B, Q, Gm))
+        if tg.cuda:
+            return match_cost(masks, coords, pl["match"], pl["code"], Gm, c_class, self.cost_class, self.cost_mask,
+                              self.cost_dice)
+        C = torch.zeros((B, Q, Gm), dtype=torch.float32)
+        for b in range(B):
+            G = tg.G[b]
+            if G == 0:
+                continue
+            x, t = masks[b].float(), pl["list"][b].float()
+            if not self._video:
+                x, t = x[:, None], t[:, None]
+            x = point_sample(x, coords[b:b + 1].expand(Q, -1, -1)).flatten(1)           # (Q, T*K)
+            t = point_sample(t, coords[b:b + 1].expand(G, -1, -1)).flatten(1)           # (G, T*K)
+            s = x.sigmoid()
+            c_mask = (F.softplus(x).sum(1)[:, None] - x @ t.t()) / x.shape[1]
+            c_dice = 1 - (2 * (s @ t.t()) + 1) / (s.sum(1)[:, None] + t.sum(1)[None] + 1)
+            C[b, :, :G] = self.cost_mask * c_mask + self.cost_class * c_class[b, :, :G] + self.cost_dice * c_dice
+        return C
+
+    @torch.no_grad()
+    def memory_efficient_forward(self, outputs, targets, prepared: MaskTargets | None = None, point_source=None):
+        masks = outputs["pred_masks"]
+        if masks.dim() != (5 if self._video else 4):
+            raise ValueError("pred_masks must be (B, Q, T, H, W)" if self._video else "pred_masks must be (B, Q, H, W)")
+        tg = prepared or MaskTargets(targets, masks.device, self._video)
+        B, Q = outputs["pred_logits"].shape[:2]
+        source = self.point_source or point_source or _rand_source
+        coords = source("match", (B, self.num_points, 2), masks.device)
+        if tg.Gm == 0:
+            e = torch.empty(0, dtype=torch.int64, device=masks.device)
+            return [(e, e) for _ in range(B)]
+        C = self.cost_matrix(outputs, tg, coords)
+        if tg.cuda:
+            match, status = ws.lsap_batched(C, cols=ws.h2d(tg.G, masks.device))
+            self.last_status = status
+        else:
+            from scipy.optimize import linear_sum_assignment
+            match = torch.full((B, Q), -1, dtype=torch.int32)
+            for b in range(B):
+                i, j = linear_sum_assignment(C[b, :, :tg.G[b]].numpy())
+                match[b, torch.as_tensor(i, dtype=torch.int64)] = torch.as_tensor(j, dtype=torch.int32)
+        return ws.indices_from_match(match, [min(Q, g) for g in tg.G])
+
+    @torch.no_grad()
+    def forward(self, outputs, targets, prepared: MaskTargets | None = None, point_source=None):
+        return self.memory_efficient_forward(outputs, targets, prepared, point_source)
+
+    def __repr__(self, _repr_indent=4):
+        head = "Matcher " + self.__class__.__name__
+        body = [f"cost_class: {self.cost_class}", f"cost_mask: {self.cost_mask}", f"cost_dice: {self.cost_dice}"]
+        return "\n".join([head] + [" " * _repr_indent + line for line in body])
+
+
+class VideoHungarianMatcher(HungarianMatcher):
+    """Reference: mask2former_video/modeling/matcher.py:503-590: the same K points in every one of the T frames,
+    sums and the divisor over T K."""
+
+    _video = True
+
+
+# ------------------------------------------------------------------------------------------------------------
+# criteria
+# ------------------------------------------------------------------------------------------------------------
+class SetCriterion(nn.Module):
+    """Reference: mask2former/modeling/criterion.py:775-955; ``losses`` is any subset of "labels", "masks"."""
+
+    _video = False
+
+    def __init__(self, num_classes, matcher, weight_dict, eos_coef, losses, num_points, oversample_ratio,
+                 importance_sample_ratio, mask_target_type="mask"):
+        super().__init__()
+        self.num_classes = num_classes
+        self.matcher = matcher
+        self.weight_dict = weight_dict
+        self.eos_coef = eos_coef
+        self.losses = losses
+        empty_weight = torch.ones(self.num_classes + 1)
+        empty_weight[-1] = self.eos_coef
+        self.register_buffer("empty_weight", empty_weight)
+        self.num_points = num_points
+        self.oversample_ratio = oversample_ratio
+        self.importance_sample_ratio = importance_sample_ratio
+        if mask_target_type not in ("mask", "box_mask"):
+            raise ValueError('mask_target_type must be "mask" or "box_mask"')
+        self.mask_target_type = mask_target_type
+        self.point_source = _rand_source
+        self.check_matching = True   # one host sync per call for scipy's ValueErrors; False skips it
+        self._tg = self._tg_key = None
+        self._status = []
+
+    # -- losses ----------------------------------------------------------------------------------------------
+    def loss_labels(self, outputs, targets, indices, num_masks):
+        src_logits = outputs["pred_logits"].float()
+        idx = self._get_src_permutation_idx(indices)
+        target_classes_o = torch.cat([t["labels"].to(src_logits.device)[J] for t, (_, J) in zip(targets, indices)])
+        target_classes = torch.full(src_logits.shape[:2], self.num_classes, dtype=torch.int64,
+                                    device=src_logits.device)
+        target_classes[idx] = target_classes_o
+        return {"loss_ce": F.cross_entropy(src_logits.transpose(1, 2), target_classes, self.empty_weight)}
+
+    def _target_key(self):
+        return "box_masks_full" if self.mask_target_type == "box_mask" else "masks"
+
+    def _sample_points(self, uncertainty, R, device):
+        """get_uncertain_point_coords_with_randomness; ``uncertainty(coords (R, P, 2)) -> (R, P)``."""
+        n_over = int(self.num_points * self.oversample_ratio)
+        n_unc = int(self.importance_sample_ratio * self.num_points)
+        n_rand = self.num_points - n_unc
+        over = self.point_source("oversample", (R, n_over, 2), device)
+        idx = torch.topk(uncertainty(over), k=n_unc, dim=1)[1]
+        coords = torch.gather(over, 1, idx[:, :, None].expand(-1, -1, 2))
+        if n_rand > 0:
+            coords = torch.cat([coords, self.point_source("random", (R, n_rand, 2), device)], dim=1)
+        return coords
+
+    def loss_masks(self, outputs, targets, indices, num_masks):
+        masks = outputs["pred_masks"]
+        dev = masks.device
+        tg = self._targets(targets, dev)
+        batch_idx, src_idx = self._get_src_permutation_idx(indices)
+        N = int(batch_idx.shape[0])
+        if N == 0 or self.num_points == 0:
+            zero = masks.flatten()[:0].float().sum()  # no matched mask: zero, still connected to pred_masks
+            return {"loss_mask": zero, "loss_dice": zero}
+        tgt_idx = torch.cat([j for (_, j) in indices])
+        pl = tg.planes(self._target_key())
+        Q = masks.shape[1]
+        T = masks.shape[2] if self._video else 1
+        if tg.cuda:
+            x = _logit_tensor(masks)
+            frames = torch.arange(T, device=dev)
+            plane = ((batch_idx * Q + src_idx)[:, None] * T + frames).reshape(-1)                    # (R,)
+            info = pl["rows"][batch_idx]                                                            # (N, 4)
+            ptr = info[:, :1] + (tgt_idx[:, None] * T + frames) * info[:, 1:2]                      # (N, T)
+            size = info[:, None, 2:4].expand(N, T, 2)
+            # the image criterion samples targets zero-padded to the batch maximum; video clips share one size
+            norm = size if self._video else torch.tensor(pl["pad"], dtype=torch.int64).pin_memory().to(
+                dev, non_blocking=True).expand(N, T, 2)
+            rows = torch.cat([ptr[:, :, None], size, norm], 2).reshape(N * T, 5)
+            with torch.no_grad():
+                coords = self._sample_points(lambda u: point_uncertainty(x.detach(), plane, u), N * T, dev)
+            bce, inter, sig, tsum = point_loss_sums(x, plane, coords, rows, pl["code"], keep=pl["list"])
+        else:
+            src = masks[batch_idx, src_idx].float()
+            Hp, Wp = pl["pad"]
+            tgt = []
+            for b, (_, j) in enumerate(indices):
+                m = pl["list"][b][j].float()
+                tgt.append(m if self._video else F.pad(m, (0, Wp - m.shape[-1], 0, Hp - m.shape[-2])))
+            tgt = torch.cat(tgt)
+            src = (src.flatten(0, 1) if self._video else src)[:, None]                              # (R, 1, H, W)
+            tgt = (tgt.flatten(0, 1) if self._video else tgt)[:, None]
+            with torch.no_grad():
+                coords = self._sample_points(lambda u: -point_sample(src, u)[:, 0].abs(), src.shape[0], dev)
+                t = point_sample(tgt, coords)[:, 0]
+            xk = point_sample(src, coords)[:, 0]
+            s = xk.sigmoid()
+            bce = F.binary_cross_entropy_with_logits(xk, t, reduction="none").sum(1)
+            inter, sig, tsum = (s * t).sum(1), s.sum(1), t.sum(1)
+        loss_mask = (bce / coords.shape[1]).sum() / num_masks
+        loss_dice = (1 - (2 * inter + 1) / (sig + tsum + 1)).sum() / num_masks
+        return {"loss_mask": loss_mask, "loss_dice": loss_dice}
+
+    def _get_src_permutation_idx(self, indices):
+        batch_idx = torch.cat([torch.full_like(src, i) for i, (src, _) in enumerate(indices)])
+        src_idx = torch.cat([src for (src, _) in indices])
+        return batch_idx, src_idx
+
+    def _get_tgt_permutation_idx(self, indices):
+        batch_idx = torch.cat([torch.full_like(tgt, i) for i, (_, tgt) in enumerate(indices)])
+        tgt_idx = torch.cat([tgt for (_, tgt) in indices])
+        return batch_idx, tgt_idx
+
+    def get_loss(self, loss, outputs, targets, indices, num_masks):
+        loss_map = {"labels": self.loss_labels, "masks": self.loss_masks}
+        assert loss in loss_map, f"do you really want to compute {loss} loss?"
+        return loss_map[loss](outputs, targets, indices, num_masks)
+
+    # -- driver ----------------------------------------------------------------------------------------------
+    def _targets(self, targets, device):
+        # built once per forward() for all heads; a direct get_loss() call outside forward builds its own
+        if self._tg is None or self._tg_key is not targets:
+            self._tg = MaskTargets(targets, device, self._video)
+            self._tg_key = targets
+        return self._tg
+
+    def _match(self, outputs, targets):
+        if isinstance(self.matcher, HungarianMatcher):
+            self.matcher.last_status = None
+            idx = self.matcher(outputs, targets, prepared=self._targets(targets, outputs["pred_masks"].device),
+                               point_source=self.point_source)
+            if self.matcher.last_status is not None:
+                self._status.append(self.matcher.last_status)
+            return idx
+        return self.matcher(outputs, targets)
+
+    def forward(self, outputs, targets):
+        self._tg = self._tg_key = None
+        self._status = []
+        try:
+            outputs_without_aux = {k: v for k, v in outputs.items() if k != "aux_outputs"}
+            indices = self._match(outputs_without_aux, targets)
+            dev = next(iter(outputs.values())).device
+            n = sum(len(t["labels"]) for t in targets)
+            world = _dist_world()
+            if world:
+                nm = torch.as_tensor([n], dtype=torch.float, device=dev)
+                torch.distributed.all_reduce(nm)
+                num_masks = torch.clamp(nm / world, min=1)[0]      # stays on the device (no .item())
+            else:
+                num_masks = max(float(np.float32(n)), 1.0)
+            losses = {}
+            for loss in self.losses:
+                losses.update(self.get_loss(loss, outputs, targets, indices, num_masks))
+            for i, aux_outputs in enumerate(outputs.get("aux_outputs", [])):
+                indices = self._match(aux_outputs, targets)
+                for loss in self.losses:
+                    l_dict = self.get_loss(loss, aux_outputs, targets, indices, num_masks)
+                    losses.update({k + f"_{i}": v for k, v in l_dict.items()})
+            if self.check_matching and self._status:
+                ws.raise_on_lsap_status(torch.stack(self._status))
+            return losses
+        finally:
+            self._tg = self._tg_key = None
+            self._status = []
+
+    def __repr__(self):
+        head = "Criterion " + self.__class__.__name__
+        body = [f"matcher: {self.matcher.__repr__(_repr_indent=8)}", f"losses: {self.losses}",
+                f"weight_dict: {self.weight_dict}", f"num_classes: {self.num_classes}", f"eos_coef: {self.eos_coef}",
+                f"num_points: {self.num_points}", f"oversample_ratio: {self.oversample_ratio}",
+                f"importance_sample_ratio: {self.importance_sample_ratio}"]
+        return "\n".join([head] + [" " * 4 + line for line in body])
+
+
+class VideoSetCriterion(SetCriterion):
+    """Reference: mask2former_video/modeling/criterion.py:144-310 (eight-argument constructor): every one of the
+    N T (matched mask, frame) rows is its own mask with its own points; targets are ``t["masks"]``."""
+
+    _video = True
+
+    def __init__(self, num_classes, matcher, weight_dict, eos_coef, losses, num_points, oversample_ratio,
+                 importance_sample_ratio):
+        super().__init__(num_classes, matcher, weight_dict, eos_coef, losses, num_points, oversample_ratio,
+                         importance_sample_ratio, "mask")

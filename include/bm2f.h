@@ -524,6 +524,48 @@ int m2f_temporal_mine(const float* feats, int T, int D, int h, int w, const int*
                       const int* blocks, int n_blocks, int* out_p1, int n_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Point sampling of the mask-supervised matcher and criterion (modeling/matcher.py:479-597,
+ * modeling/criterion.py:775-955 and their mask2former_video twins).  Common conventions:
+ *   point_sample(x, u), u = (ux, uy) normalised: grid_sample(bilinear, zeros, align_corners=False), i.e.
+ *          pixel (ux * Wn - 0.5, uy * Hn - 0.5); a corner outside the plane contributes 0;
+ *   masks  (n_planes, H, W) logits of `dtype` (M2F_F32 / M2F_F16 / M2F_BF16), evaluated in fp32;
+ *   tgt_dtype  0: uint8 / bool planes, 1: fp32 planes, read in place through int64 pointer tables;
+ *   H * W < 2^31 for every plane; plane offsets are 64-bit.  Nothing synchronises with the host.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Floats of workspace m2f_point_match_cost needs. */
+int m2f_point_match_workspace(int B, int T, int Q, int Gm, int K, int64_t* floats);
+/* cost (B, Q, Gm) fp32 = w_mask * (sum softplus(x) - sum x t) / (T K) + w_class * cost_class +
+ * w_dice * (1 - (2 sum sig(x) t + 1) / (sum sig(x) + sum t + 1)), sums over the T frames and the K points
+ * coords (B, K, 2) of image b, shared by its Q predictions masks (B, Q, T, H, W) and its targets.
+ * tgt (B, 4) int64 device table [pointer to (G_b, T, Ht, Wt) planes, G_b, Ht, Wt]: targets are sampled at
+ * their own size.  Columns g >= G_b are 0.  cost_class (B, Q, Gm) fp32 may be NULL.  Per-tile partial
+ * sums go through `workspace` and are reduced in a fixed order in fp64: bitwise repeatable. */
+int m2f_point_match_cost(const void* masks, int dtype, int B, int Q, int T, int H, int W, const float* coords,
+                         int K, const int64_t* tgt, int tgt_dtype, int Gm, const float* cost_class,
+                         float w_class, float w_mask, float w_dice, float* workspace, int64_t ws_floats,
+                         float* cost, void* stream);
+/* out (R, P) fp32 = -|point_sample(masks[plane[r]], coords[r, p])|, coords (R, P, 2), plane (R,) int64
+ * (a row whose plane is outside [0, n_planes) gets 0). */
+int m2f_point_uncertainty(const void* masks, int dtype, int64_t n_planes, int H, int W, const int64_t* plane,
+                          int R, const float* coords, int P, float* out, void* stream);
+/* Chunks of points per row of m2f_point_loss_fwd's partials. */
+int m2f_point_loss_chunks(int K);
+/* part (R, chunks, 4) fp32: per row and chunk of its K points coords (R, K, 2), the sums of
+ * BCE-with-logits(x, t), sig(x) t, sig(x) and t, x = point_sample(masks[plane[r]]), t = point_sample of
+ * the row's target.  tgt (R, 5) int64 device table [plane pointer, Ht, Wt, Hn, Wn]: the target is
+ * (Ht, Wt) and the coordinates are normalised over (Hn, Wn) >= (Ht, Wt), as if zero-padded to it. */
+int m2f_point_loss_fwd(const void* masks, int dtype, int64_t n_planes, int H, int W, const int64_t* plane, int R,
+                       const float* coords, int K, const int64_t* tgt, int tgt_dtype, float* part,
+                       void* stream);
+/* grad (n_planes, H, W) fp32, zeroed by the caller, += d / d masks of sum_r (grad_rows[r, 0] BCE_r +
+ * grad_rows[r, 1] sum sig(x) t + grad_rows[r, 2] sum sig(x)), scattered through the bilinear weights
+ * with fp32 atomics (the sum order, hence the last bits, varies from run to run). */
+int m2f_point_loss_bwd(const void* masks, int dtype, int64_t n_planes, int H, int W, const int64_t* plane, int R,
+                       const float* coords, int K, const int64_t* tgt, int tgt_dtype, const float* grad_rows,
+                       float* grad, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Inference heads: the eval branch of MaskFormer.forward (maskformer_model.py:333-377) from the
  * decoder's low-resolution mask logits.  Common arguments:
  *   logits (B, Q, in_h, in_w) of `dtype` (M2F_F32 / M2F_F16 / M2F_BF16), converted to fp32 on load;
