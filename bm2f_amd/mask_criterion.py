@@ -45,15 +45,13 @@ from __future__ import annotations
 
 import ctypes
 
-import numpy as np
 import torch
 import torch.nn.functional as F
-from torch import nn
 from torch.autograd import Function
 
 from . import _native
 from . import weaksup as ws
-from .criterion import _dist_world
+from .set_criterion import _class_cost, _Matcher, _SetCriterion, _Targets
 
 _DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
@@ -75,32 +73,15 @@ def _logit_tensor(masks):
     return masks.contiguous()
 
 
-class MaskTargets:
+class MaskTargets(_Targets):
     """Per-call target tensors shared by the matcher and the mask loss of all decoder heads.  The masks are kept as
     they are (bool viewed as uint8, uint8 or fp32; anything else is converted to fp32 once) and addressed by the
     kernels through pointer tables built here without a host synchronisation."""
 
     def __init__(self, targets, device, video):
-        self.device = torch.device(device)
-        self.cuda = self.device.type == "cuda"
+        super().__init__(targets, device)
         self.video = video
-        self.B = len(targets)
-        self.G = [int(t["labels"].shape[0]) for t in targets]
-        self.Gm = max(self.G) if self.G else 0
-        self.offsets = np.concatenate([[0], np.cumsum(self.G)]).astype(np.int64).tolist()
-        self.labels = [t["labels"].to(device) for t in targets]
-        self._targets = targets
         self._planes = {}
-        self._labels_padded = None
-
-    def labels_padded(self):
-        if self._labels_padded is None:
-            lab = torch.zeros((self.B, self.Gm), dtype=torch.int64, device=self.device)
-            for b, l in enumerate(self.labels):
-                if self.G[b]:
-                    lab[b, :self.G[b]] = l
-            self._labels_padded = lab
-        return self._labels_padded
 
     def planes(self, key="masks"):
         """dict: ``list`` per-image planes (G, [T,] Ht, Wt), ``code`` 0 uint8 / 1 fp32, ``sizes`` (Ht, Wt) per
@@ -229,7 +210,7 @@ def point_loss_sums(masks, plane, coords, tgt_rows, tgt_code, keep=None):
 # ------------------------------------------------------------------------------------------------------------
 # matchers
 # ------------------------------------------------------------------------------------------------------------
-class HungarianMatcher(nn.Module):
+class HungarianMatcher(_Matcher):
     """Reference: mask2former/modeling/matcher.py:479-597 (same arguments; no buffers)."""
 
     _video = False
@@ -242,7 +223,6 @@ class HungarianMatcher(nn.Module):
         assert cost_class != 0 or cost_mask != 0 or cost_dice != 0, "all costs cant be 0"
         self.num_points = num_points
         self.point_source = None     # None: the caller's (a criterion's) source, else torch.rand
-        self.last_status = None
 
     @torch.no_grad()
     def cost_matrix(self, outputs, tg: MaskTargets, coords) -> torch.Tensor:
@@ -251,8 +231,7 @@ class HungarianMatcher(nn.Module):
         B, Q = logits.shape[:2]
         Gm = tg.Gm
         pl = tg.planes("masks")
-        prob = logits.float().softmax(-1)
-        c_class = -torch.gather(prob, 2, tg.labels_padded()[:, None, :].expand(B, Q, Gm))
+        c_class = _class_cost(logits, tg.labels_padded())
         if tg.cuda:
             return match_cost(masks, coords, pl["match"], pl["code"], Gm, c_class, self.cost_class, self.cost_mask,
                               self.cost_dice)
@@ -278,32 +257,17 @@ class HungarianMatcher(nn.Module):
         if masks.dim() != (5 if self._video else 4):
             raise ValueError("pred_masks must be (B, Q, T, H, W)" if self._video else "pred_masks must be (B, Q, H, W)")
         tg = prepared or MaskTargets(targets, masks.device, self._video)
-        B, Q = outputs["pred_logits"].shape[:2]
         source = self.point_source or point_source or _rand_source
-        coords = source("match", (B, self.num_points, 2), masks.device)
-        if tg.Gm == 0:
-            e = torch.empty(0, dtype=torch.int64, device=masks.device)
-            return [(e, e) for _ in range(B)]
-        C = self.cost_matrix(outputs, tg, coords)
-        if tg.cuda:
-            match, status = ws.lsap_batched(C, cols=ws.h2d(tg.G, masks.device))
-            self.last_status = status
-        else:
-            from scipy.optimize import linear_sum_assignment
-            match = torch.full((B, Q), -1, dtype=torch.int32)
-            for b in range(B):
-                i, j = linear_sum_assignment(C[b, :, :tg.G[b]].numpy())
-                match[b, torch.as_tensor(i, dtype=torch.int64)] = torch.as_tensor(j, dtype=torch.int32)
-        return ws.indices_from_match(match, [min(Q, g) for g in tg.G])
+        # drawn before the no-target return: one "match" draw per head whatever the targets
+        coords = source("match", (outputs["pred_logits"].shape[0], self.num_points, 2), masks.device)
+        return self._assign(outputs, tg, coords)
 
     @torch.no_grad()
     def forward(self, outputs, targets, prepared: MaskTargets | None = None, point_source=None):
         return self.memory_efficient_forward(outputs, targets, prepared, point_source)
 
     def __repr__(self, _repr_indent=4):
-        head = "Matcher " + self.__class__.__name__
-        body = [f"cost_class: {self.cost_class}", f"cost_mask: {self.cost_mask}", f"cost_dice: {self.cost_dice}"]
-        return "\n".join([head] + [" " * _repr_indent + line for line in body])
+        return self._repr(("cost_class", "cost_mask", "cost_dice"), _repr_indent)
 
 
 class VideoHungarianMatcher(HungarianMatcher):
@@ -316,22 +280,16 @@ class VideoHungarianMatcher(HungarianMatcher):
 # ------------------------------------------------------------------------------------------------------------
 # criteria
 # ------------------------------------------------------------------------------------------------------------
-class SetCriterion(nn.Module):
+class SetCriterion(_SetCriterion):
     """Reference: mask2former/modeling/criterion.py:775-955; ``losses`` is any subset of "labels", "masks"."""
 
     _video = False
+    _matcher_class = HungarianMatcher
+    _loss_table = {"labels": "loss_labels", "masks": "loss_masks"}
 
     def __init__(self, num_classes, matcher, weight_dict, eos_coef, losses, num_points, oversample_ratio,
                  importance_sample_ratio, mask_target_type="mask"):
-        super().__init__()
-        self.num_classes = num_classes
-        self.matcher = matcher
-        self.weight_dict = weight_dict
-        self.eos_coef = eos_coef
-        self.losses = losses
-        empty_weight = torch.ones(self.num_classes + 1)
-        empty_weight[-1] = self.eos_coef
-        self.register_buffer("empty_weight", empty_weight)
+        super().__init__(num_classes, matcher, weight_dict, eos_coef, losses)
         self.num_points = num_points
         self.oversample_ratio = oversample_ratio
         self.importance_sample_ratio = importance_sample_ratio
@@ -339,20 +297,8 @@ class SetCriterion(nn.Module):
             raise ValueError('mask_target_type must be "mask" or "box_mask"')
         self.mask_target_type = mask_target_type
         self.point_source = _rand_source
-        self.check_matching = True   # one host sync per call for scipy's ValueErrors; False skips it
-        self._tg = self._tg_key = None
-        self._status = []
 
     # -- losses ----------------------------------------------------------------------------------------------
-    def loss_labels(self, outputs, targets, indices, num_masks):
-        src_logits = outputs["pred_logits"].float()
-        idx = self._get_src_permutation_idx(indices)
-        target_classes_o = torch.cat([t["labels"].to(src_logits.device)[J] for t, (_, J) in zip(targets, indices)])
-        target_classes = torch.full(src_logits.shape[:2], self.num_classes, dtype=torch.int64,
-                                    device=src_logits.device)
-        target_classes[idx] = target_classes_o
-        return {"loss_ce": F.cross_entropy(src_logits.transpose(1, 2), target_classes, self.empty_weight)}
-
     def _target_key(self):
         return "box_masks_full" if self.mask_target_type == "box_mask" else "masks"
 
@@ -416,76 +362,17 @@ class SetCriterion(nn.Module):
         loss_dice = (1 - (2 * inter + 1) / (sig + tsum + 1)).sum() / num_masks
         return {"loss_mask": loss_mask, "loss_dice": loss_dice}
 
-    def _get_src_permutation_idx(self, indices):
-        batch_idx = torch.cat([torch.full_like(src, i) for i, (src, _) in enumerate(indices)])
-        src_idx = torch.cat([src for (src, _) in indices])
-        return batch_idx, src_idx
-
-    def _get_tgt_permutation_idx(self, indices):
-        batch_idx = torch.cat([torch.full_like(tgt, i) for i, (_, tgt) in enumerate(indices)])
-        tgt_idx = torch.cat([tgt for (_, tgt) in indices])
-        return batch_idx, tgt_idx
-
-    def get_loss(self, loss, outputs, targets, indices, num_masks):
-        loss_map = {"labels": self.loss_labels, "masks": self.loss_masks}
-        assert loss in loss_map, f"do you really want to compute {loss} loss?"
-        return loss_map[loss](outputs, targets, indices, num_masks)
-
     # -- driver ----------------------------------------------------------------------------------------------
-    def _targets(self, targets, device):
-        # built once per forward() for all heads; a direct get_loss() call outside forward builds its own
-        if self._tg is None or self._tg_key is not targets:
-            self._tg = MaskTargets(targets, device, self._video)
-            self._tg_key = targets
-        return self._tg
+    def _make_targets(self, targets, device):
+        return MaskTargets(targets, device, self._video)
 
-    def _match(self, outputs, targets):
-        if isinstance(self.matcher, HungarianMatcher):
-            self.matcher.last_status = None
-            idx = self.matcher(outputs, targets, prepared=self._targets(targets, outputs["pred_masks"].device),
-                               point_source=self.point_source)
-            if self.matcher.last_status is not None:
-                self._status.append(self.matcher.last_status)
-            return idx
-        return self.matcher(outputs, targets)
+    def _matcher_kwargs(self):
+        return {"point_source": self.point_source}
 
-    def forward(self, outputs, targets):
-        self._tg = self._tg_key = None
-        self._status = []
-        try:
-            outputs_without_aux = {k: v for k, v in outputs.items() if k != "aux_outputs"}
-            indices = self._match(outputs_without_aux, targets)
-            dev = next(iter(outputs.values())).device
-            n = sum(len(t["labels"]) for t in targets)
-            world = _dist_world()
-            if world:
-                nm = torch.as_tensor([n], dtype=torch.float, device=dev)
-                torch.distributed.all_reduce(nm)
-                num_masks = torch.clamp(nm / world, min=1)[0]      # stays on the device (no .item())
-            else:
-                num_masks = max(float(np.float32(n)), 1.0)
-            losses = {}
-            for loss in self.losses:
-                losses.update(self.get_loss(loss, outputs, targets, indices, num_masks))
-            for i, aux_outputs in enumerate(outputs.get("aux_outputs", [])):
-                indices = self._match(aux_outputs, targets)
-                for loss in self.losses:
-                    l_dict = self.get_loss(loss, aux_outputs, targets, indices, num_masks)
-                    losses.update({k + f"_{i}": v for k, v in l_dict.items()})
-            if self.check_matching and self._status:
-                ws.raise_on_lsap_status(torch.stack(self._status))
-            return losses
-        finally:
-            self._tg = self._tg_key = None
-            self._status = []
-
-    def __repr__(self):
-        head = "Criterion " + self.__class__.__name__
-        body = [f"matcher: {self.matcher.__repr__(_repr_indent=8)}", f"losses: {self.losses}",
-                f"weight_dict: {self.weight_dict}", f"num_classes: {self.num_classes}", f"eos_coef: {self.eos_coef}",
-                f"num_points: {self.num_points}", f"oversample_ratio: {self.oversample_ratio}",
-                f"importance_sample_ratio: {self.importance_sample_ratio}"]
-        return "\n".join([head] + [" " * 4 + line for line in body])
+    def _repr_body(self):
+        return super()._repr_body() + [f"num_points: {self.num_points}",
+                                       f"oversample_ratio: {self.oversample_ratio}",
+                                       f"importance_sample_ratio: {self.importance_sample_ratio}"]
 
 
 class VideoSetCriterion(SetCriterion):

@@ -35,25 +35,19 @@ sync per call (``check_matching = False`` skips it).
 
 On CPU tensors the same classes evaluate the same definition in plain torch (scipy for the assignment), so the
 host logic is testable without a GPU.  That is not a fall-back: on a HIP tensor a kernel error raises.
+
+The matcher and the targets also serve the image criterion (criterion.py) as the one-frame case: targets and masks
+without a frame axis.  The driver shared with the other criterion families is set_criterion.py.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 import torch.nn.functional as F
-from torch import nn
+from torch.nn.utils.rnn import pad_sequence
 
 from . import weaksup as ws
-from .criterion import _dice_cost, _dist_world, _IterMirror
-
-
-class _IterCounter(_IterMirror):
-    """``_IterMirror`` with a read that does not increment (the criterion steps at the end of forward)."""
-
-    def peek(self, buf):
-        if self.value is None:
-            self.value = float(buf.item())       # once after construction / load_state_dict
-        return self.value
+from .set_criterion import _bit_planes, _class_cost, _dice_cost, _IterMirror, _Matcher, _SetCriterion, _Targets
 
 
 def _neighbours(x, d):
@@ -78,68 +72,69 @@ def _bits_torch(sim, thr):
     return ((sim >= thr).to(torch.int32) << k).sum(1).to(torch.uint8)
 
 
-class VideoWeakTargets:
+def _frames_side_by_side(v, B, T):
+    """Per-frame rows (B*T, N, L) -> (B, N, T*L); one frame is returned as it is."""
+    if T == 1:
+        return v
+    return v.view(B, T, v.shape[1], -1).transpose(1, 2).reshape(B, v.shape[1], -1)
+
+
+class VideoWeakTargets(_Targets):
     """Per-call target tensors shared by the matcher and every loss of all decoder heads: padded boxes, neighbour
-    bits, extents, pairwise denominators and the packed temporal pairs."""
+    bits, extents, pairwise denominators and the packed temporal pairs.  Targets without a frame axis (``box_masks``
+    (G, H, W), similarity (G, 8, H, W): criterion.WeakTargets) are clips of one frame."""
+
+    _sim_key = "color_similarities"
 
     def __init__(self, targets, device, thresh, need_sim=True):
-        self.device = device
-        self.cuda = torch.device(device).type == "cuda"
+        super().__init__(targets, device)
         self.thresh = thresh
-        self.B = len(targets)
-        self.G = [int(t["labels"].shape[0]) for t in targets]
-        self.Gm = max(self.G) if self.G else 0
-        self.offsets = np.concatenate([[0], np.cumsum(self.G)]).astype(np.int64).tolist()
-        self.labels = [t["labels"].to(device) for t in targets]
-        self.box_list = [t["box_masks"].to(device=device, dtype=torch.float32) for t in targets]   # (G, T, H, W)
-        self.T, self.H, self.W = (int(v) for v in self.box_list[0].shape[1:]) if self.box_list else (0, 0, 0)
+        self.box_list = [t["box_masks"].to(device=device, dtype=torch.float32) for t in targets]  # (G, [T,] H, W)
+        self.T, self.H, self.W = 0, 0, 0
+        if self.box_list:
+            self.T = int(self.box_list[0].shape[1]) if self.box_list[0].dim() == 4 else 1
+            self.H, self.W = (int(v) for v in self.box_list[0].shape[-2:])
         T, H, W = self.T, self.H, self.W
         self.box_all = torch.cat(self.box_list).reshape(-1, H, W).contiguous() if self.box_list else None  # (Gt*T,..)
         self.bits = self.sim_list = None
         self.shared = True
         if need_sim:
-            sims = [t["color_similarities"] for t in targets]
+            sims = [t[self._sim_key] for t in targets]                                           # (G, [T,] 8, H, W)
             self.shared = all(s.shape[0] <= 1 or s.stride(0) == 0 for s in sims)
             to_bits = ws.threshold_bits if self.cuda else _bits_torch
             if self.shared:
                 # the frame's one map shared across instances -> bits per (clip, frame)
-                img = [s[0] if s.shape[0] else s.new_zeros((T, 8, H, W)) for s in sims]
-                img = torch.stack([s.to(device=device, dtype=torch.float32) for s in img])       # (B, T, 8, H, W)
+                one = tuple(self.box_list[0].shape[1:-2]) + (8, H, W)
+                img = [s[0] if s.shape[0] else s.new_zeros(one) for s in sims]
+                img = torch.stack([s.to(device=device, dtype=torch.float32) for s in img])       # (B, [T,] 8, H, W)
                 self.bits = to_bits(img.reshape(self.B * T, 8, H, W).contiguous(), thresh)       # (B*T, H, W)
             else:
                 self.sim_list = [s.to(device=device, dtype=torch.float32) for s in sims]
                 sim_all = torch.cat(self.sim_list).reshape(-1, 8, H, W)
                 self.bits = to_bits(sim_all.contiguous(), thresh) if sim_all.shape[0] else None  # (Gt*T, H, W)
-        self._targets = targets
-        self._padded = self._match_aux = self._pairs = None
+        self._box_padded = self._match_aux = self._pairs = None
 
-    def padded(self):
-        """labels (B, Gm) and boxes as frames-as-images (B*T, Gm, H, W)."""
-        if self._padded is None:
-            B, Gm, T = self.B, self.Gm, self.T
-            labels = torch.zeros((B, Gm), dtype=torch.int64, device=self.device)
-            box = torch.zeros((B, T, Gm, self.H, self.W), dtype=torch.float32, device=self.device)
-            for b in range(B):
-                if self.G[b]:
-                    labels[b, :self.G[b]] = self.labels[b]
-                    box[b, :, :self.G[b]] = self.box_list[b].transpose(0, 1)
-            self._padded = (labels, box.view(B * T, Gm, self.H, self.W))
-        return self._padded
+    def box_padded(self):
+        """The boxes as frames-as-images (B*T, Gm, H, W), zero beyond a clip's G."""
+        if self._box_padded is None:
+            box = pad_sequence(self.box_list, batch_first=True).view(self.B, self.Gm, self.T, self.H, self.W)
+            self._box_padded = box.transpose(1, 2).reshape(self.B * self.T, self.Gm, self.H, self.W)
+        return self._box_padded
 
     def match_aux(self):
+        """Matcher-side constants of the targets: box axis projections, the pairwise normaliser
+        sum_p box_g(p) popcount(bits(p)) (shared similarity) and the per-frame target counts."""
         if self._match_aux is None:
-            _, box = self.padded()
+            box = self.box_padded()
             B, Gm, T = self.B, self.Gm, self.T
-            bx = box.amax(3).view(B, T, Gm, -1).transpose(1, 2).reshape(B, Gm, -1)      # (B, Gm, T*H)
-            by = box.amax(2).view(B, T, Gm, -1).transpose(1, 2).reshape(B, Gm, -1)      # (B, Gm, T*W)
-            aux = {"box_x": bx, "box_y": by}
+            aux = {"box_x": _frames_side_by_side(box.amax(3), B, T),        # (B, Gm, T*H)
+                   "box_y": _frames_side_by_side(box.amax(2), B, T)}        # (B, Gm, T*W)
             if self.cuda:
                 aux["gcount"] = ws.h2d(np.repeat(self.G, T).tolist(), self.device)
                 aux["extents"] = ws.box_extents(box)
             if self.shared and self.bits is not None:
-                k = torch.arange(8, device=box.device, dtype=torch.uint8)
-                tsum = ((self.bits.view(B * T, -1, 1) >> k) & 1).sum(-1, dtype=torch.float32)      # (B*T, HW)
-                aux["pair_den"] = (box.view(B * T, Gm, -1) * tsum[:, None]).sum(-1).clamp(min=1.0)  # (B*T, Gm)
+                tsum = _bit_planes(self.bits).sum(1, dtype=torch.float32).view(B * T, 1, -1)       # (B*T, 1, HW)
+                aux["pair_den"] = (box.view(B * T, Gm, -1) * tsum).sum(-1).clamp(min=1.0)          # (B*T, Gm)
             self._match_aux = aux
         return self._match_aux
 
@@ -153,9 +148,13 @@ class VideoWeakTargets:
         return self._pairs
 
 
-class VideoHungarianMatcherProjPair(nn.Module):
+class VideoHungarianMatcherProjPair(_Matcher):
     """Reference: mask2former_video/modeling/matcher.py:249-393 (same arguments and ``_iter`` buffer);
-    ``cost_pairwise = 0`` is ``VideoHungarianMatcherProj`` (:396-501)."""
+    ``cost_pairwise = 0`` is ``VideoHungarianMatcherProj`` (:396-501).  Masks without a frame axis, (B, Q, H, W),
+    are one-frame clips: the image matcher (criterion.HungarianMatcherProjPair)."""
+
+    _repr_fields = ("cost_class", "cost_projection", "cost_pairwise", "pairwise_size", "pairwise_dilation",
+                    "pairwise_color_thresh")
 
     def __init__(self, cost_class: float = 1, cost_projection: float = 1, cost_pairwise: float = 1,
                  pairwise_size: int = 3, pairwise_dilation: int = 2, pairwise_color_thresh: float = 0.3,
@@ -173,7 +172,6 @@ class VideoHungarianMatcherProjPair(nn.Module):
             raise ValueError("only pairwise_size 3 is implemented")
         self.register_buffer("_iter", torch.zeros([1]), persistent=_persistent_iter)
         self._iter_host = _IterMirror(self)
-        self.last_status = None
 
     def _prepare(self, targets, device):
         return VideoWeakTargets(targets, device, self.pairwise_color_thresh, need_sim=self.cost_pairwise != 0)
@@ -182,28 +180,32 @@ class VideoHungarianMatcherProjPair(nn.Module):
     def cost_matrix(self, outputs, tg: VideoWeakTargets, warm: float) -> torch.Tensor:
         """(B, Q, Gm) fp32 matching cost of every clip (columns >= G_b are padding)."""
         logits, masks = outputs["pred_logits"], outputs["pred_masks"]
-        B, Q, T, H, W = masks.shape
-        labels, box = tg.padded()
+        B, Q = masks.shape[:2]
+        T, H, W = tg.T, *masks.shape[-2:]
+        box = tg.box_padded()
         aux = tg.match_aux()
         Gm = tg.Gm
-        prob = logits.float().softmax(-1)
-        c_class = -torch.gather(prob, 2, labels[:, None, :].expand(B, Q, Gm))
-        # frames as images: the one fp32 cast-and-permute of the masks
-        x = torch.empty((B, T, Q, H, W), dtype=torch.float32, device=masks.device)
-        x = x.copy_(masks.transpose(1, 2)).view(B * T, Q, H, W)
+        c_class = _class_cost(logits, tg.labels_padded())
+        if masks.dim() == 4:
+            x = masks.float().contiguous()          # an image: fp32 contiguous masks are read in place
+        else:
+            # frames as images: the one fp32 cast-and-permute of the masks
+            x = torch.empty((B, T, Q, H, W), dtype=torch.float32, device=masks.device)
+            x = x.copy_(masks.transpose(1, 2)).view(B * T, Q, H, W)
         want_pair = self.cost_pairwise != 0 and warm != 0
         pair = None
         if tg.cuda and tg.shared and tg.bits is not None:
             # one pass: per-frame pairwise numerators and both axis projections
             num, sx, sy = ws.match_cost(x, tg.bits, box, aux["gcount"], self.pairwise_dilation, aux["extents"])
-            pair = (num / aux["pair_den"][:, None, :]).view(B, T, Q, Gm).mean(1)
+            pair = num / aux["pair_den"][:, None, :]
+            if T > 1:
+                pair = pair.view(B, T, Q, Gm).mean(1)
         else:
             sx, sy = x.amax(3), x.amax(2)
             if want_pair:
                 pair = self._pairwise_cost_general(x, tg)
-        sx = sx.view(B, T, Q, H).transpose(1, 2).reshape(B, Q, T * H)
-        sy = sy.view(B, T, Q, W).transpose(1, 2).reshape(B, Q, T * W)
-        c_proj = _dice_cost(sx, aux["box_x"]) + _dice_cost(sy, aux["box_y"])
+        c_proj = _dice_cost(_frames_side_by_side(sx, B, T), aux["box_x"]) + \
+            _dice_cost(_frames_side_by_side(sy, B, T), aux["box_y"])
         C = self.cost_class * c_class + self.cost_projection * c_proj
         if want_pair:
             C = C + self.cost_pairwise * (pair * warm)
@@ -220,39 +222,24 @@ class VideoHungarianMatcherProjPair(nn.Module):
             G = tg.G[b]
             if G == 0:
                 continue
-            box = tg.box_list[b]                                                  # (G, T, H, W)
+            box = tg.box_list[b].view(G, T, H, W)
+            sim = None if tg.shared else tg.sim_list[b].view(G, T, 8, H, W)
             for t in range(T):
                 xf = x[b * T + t].contiguous()
                 s = (ws.pairwise_planes(xf, d) if tg.cuda else _pred_similarity(xf, d)).view(Q, -1)
                 if tg.shared:
-                    k = torch.arange(8, device=x.device, dtype=torch.uint8).view(8, 1, 1)
-                    on = ((tg.bits[b * T + t][None] >> k) & 1).float()[None].expand(G, 8, H, W)
+                    on = _bit_planes(tg.bits[b * T + t][None]).float().expand(G, 8, H, W)
                 else:
-                    on = (tg.sim_list[b][:, t] >= tg.thresh).float()
+                    on = (sim[:, t] >= tg.thresh).float()
                 tt = (on * box[:, t, None]).reshape(G, -1)
                 out[b, :, :G] += (s @ tt.t()) / tt.sum(1)[None].clamp(min=1.0)
-        return out / T
+        return out.div_(T) if T > 1 else out
 
     @torch.no_grad()
     def memory_efficient_forward(self, outputs, targets, prepared: VideoWeakTargets | None = None):
-        masks = outputs["pred_masks"]
-        tg = prepared or self._prepare(targets, masks.device)
-        B, Q = outputs["pred_logits"].shape[:2]
-        if tg.Gm == 0:
-            e = torch.empty(0, dtype=torch.int64, device=masks.device)
-            return [(e, e) for _ in range(B)]
+        tg = prepared or self._prepare(targets, outputs["pred_masks"].device)
         warm = min(self._iter_host.value / float(self.pairwise_warmup_iters), 1.0)
-        C = self.cost_matrix(outputs, tg, warm)
-        if tg.cuda:
-            match, status = ws.lsap_batched(C, cols=ws.h2d(tg.G, masks.device))
-            self.last_status = status
-        else:
-            from scipy.optimize import linear_sum_assignment
-            match = torch.full((B, Q), -1, dtype=torch.int32)
-            for b in range(B):
-                i, j = linear_sum_assignment(C[b, :, :tg.G[b]].numpy())
-                match[b, torch.as_tensor(i, dtype=torch.int64)] = torch.as_tensor(j, dtype=torch.int32)
-        return ws.indices_from_match(match, [min(Q, g) for g in tg.G])
+        return self._assign(outputs, tg, warm)
 
     @torch.no_grad()
     def forward(self, outputs, targets, prepared: VideoWeakTargets | None = None):
@@ -260,77 +247,40 @@ class VideoHungarianMatcherProjPair(nn.Module):
         return self.memory_efficient_forward(outputs, targets, prepared)
 
     def __repr__(self, _repr_indent=4):
-        head = "Matcher " + self.__class__.__name__
-        body = [f"cost_class: {self.cost_class}", f"cost_projection: {self.cost_projection}",
-                f"cost_pairwise: {self.cost_pairwise}", f"pairwise_size: {self.pairwise_size}",
-                f"pairwise_dilation: {self.pairwise_dilation}",
-                f"pairwise_color_thresh: {self.pairwise_color_thresh}"]
-        return "\n".join([head] + [" " * _repr_indent + line for line in body])
+        return self._repr(self._repr_fields, _repr_indent)
 
 
 class VideoHungarianMatcherProj(VideoHungarianMatcherProjPair):
     """Reference: matcher.py:396-501 (class and projection costs only; no ``_iter`` in its state dict)."""
 
+    _repr_fields = ("cost_class", "cost_projection")
+
     def __init__(self, cost_class: float = 1, cost_projection: float = 1):
         assert cost_class != 0 or cost_projection != 0, "all costs cant be 0"
         super().__init__(cost_class, cost_projection, 0, _persistent_iter=False)
 
-    def __repr__(self, _repr_indent=4):
-        head = "Matcher " + self.__class__.__name__
-        body = [f"cost_class: {self.cost_class}", f"cost_projection: {self.cost_projection}"]
-        return "\n".join([head] + [" " * _repr_indent + line for line in body])
 
-
-class VideoSetCriterionProjSpatPairTempPair(nn.Module):
+class VideoSetCriterionProjSpatPairTempPair(_SetCriterion):
     """Reference: criterion_proj_spatpair_temppair.py:72-406; ``losses`` is any subset of "labels",
     "projection_masks", "spatial_pairwise", "temporal_pairwise"."""
 
+    _matcher_class = VideoHungarianMatcherProjPair
+    _loss_table = {"labels": "loss_labels", "projection_masks": "loss_projection_masks",
+                   "spatial_pairwise": "loss_spatial_pairwise", "temporal_pairwise": "loss_temporal_pairwise"}
+
     def __init__(self, num_classes, matcher, weight_dict, eos_coef, pairwise_size, pairwise_dilation,
                  pairwise_color_thresh, pairwise_warmup_iters, losses):
-        super().__init__()
-        self.num_classes = num_classes
-        self.matcher = matcher
-        self.weight_dict = weight_dict
-        self.eos_coef = eos_coef
+        super().__init__(num_classes, matcher, weight_dict, eos_coef, losses)
         self.pairwise_size = pairwise_size
         self.pairwise_dilation = pairwise_dilation
         self.pairwise_color_thresh = pairwise_color_thresh
         self.pairwise_warmup_iters = pairwise_warmup_iters
-        self.losses = losses
         if pairwise_size != 3:
             raise ValueError("only pairwise_size 3 is implemented")
-        empty_weight = torch.ones(self.num_classes + 1)
-        empty_weight[-1] = self.eos_coef
-        self.register_buffer("empty_weight", empty_weight)
         self.register_buffer("_iter", torch.zeros([1]))
-        self._iter_host = _IterCounter(self)
-        self.check_matching = True   # one host sync per call (matcher status, pair validity); False skips it
-        self._tg = self._tg_key = None
-        self._status = []
-        self._gathered = {}
+        self._iter_host = _IterMirror(self)
 
     # -- losses ------------------------------------------------------------------------------------------
-    def loss_labels(self, outputs, targets, indices, num_masks):
-        src_logits = outputs["pred_logits"].float()
-        idx = self._get_src_permutation_idx(indices)
-        target_classes_o = torch.cat([t["labels"].to(src_logits.device)[J] for t, (_, J) in zip(targets, indices)])
-        target_classes = torch.full(src_logits.shape[:2], self.num_classes, dtype=torch.int64,
-                                    device=src_logits.device)
-        target_classes[idx] = target_classes_o
-        return {"loss_ce": F.cross_entropy(src_logits.transpose(1, 2), target_classes, self.empty_weight)}
-
-    def _matched(self, outputs, targets, indices):
-        """Matched masks (N, T, H, W) fp32 and flat target rows, gathered once per head for all mask losses."""
-        tg = self._targets(targets, outputs["pred_masks"].device)
-        key = (id(outputs["pred_masks"]), id(indices))
-        hit = self._gathered.get(key)
-        if hit is not None and hit[0] is outputs["pred_masks"] and hit[1] is indices:
-            return tg, hit[2], hit[3]
-        src = outputs["pred_masks"][self._get_src_permutation_idx(indices)].float().contiguous()
-        flat = torch.cat([j + tg.offsets[b] for b, (_, j) in enumerate(indices)])
-        self._gathered[key] = (outputs["pred_masks"], indices, src, flat)
-        return tg, src, flat
-
     @staticmethod
     def _zero(device):
         return torch.tensor([0], dtype=torch.float32, device=device)
@@ -374,8 +324,7 @@ class VideoSetCriterionProjSpatPairTempPair(nn.Module):
             num, den = ws.pairwise_sums(rows, tg.bits, t_row.to(torch.int32).contiguous(), tg.box_all,
                                         box_row.to(torch.int32).contiguous(), self.pairwise_dilation)
         else:
-            k = torch.arange(8, dtype=torch.uint8).view(1, 8, 1, 1)
-            on = ((tg.bits[t_row][:, None] >> k) & 1).float() * tg.box_all[box_row][:, None]
+            on = _bit_planes(tg.bits[t_row]).float() * tg.box_all[box_row][:, None]
             num = (_pred_similarity(rows, self.pairwise_dilation) * on).flatten(1).sum(1)
             den = on.flatten(1).sum(1)
         loss = (num / den.clamp(min=1.0)).view(N, T).mean(1).sum() / num_masks
@@ -393,40 +342,10 @@ class VideoSetCriterionProjSpatPairTempPair(nn.Module):
         loss = total / count.to(torch.float32).clamp(min=1.0)
         return {"loss_mask_temporal_pairwise": loss * self._warm()}
 
-    def _get_src_permutation_idx(self, indices):
-        batch_idx = torch.cat([torch.full_like(src, i) for i, (src, _) in enumerate(indices)])
-        src_idx = torch.cat([src for (src, _) in indices])
-        return batch_idx, src_idx
-
-    def _get_tgt_permutation_idx(self, indices):
-        batch_idx = torch.cat([torch.full_like(tgt, i) for i, (_, tgt) in enumerate(indices)])
-        tgt_idx = torch.cat([tgt for (_, tgt) in indices])
-        return batch_idx, tgt_idx
-
-    def get_loss(self, loss, outputs, targets, indices, num_masks):
-        loss_map = {"labels": self.loss_labels, "projection_masks": self.loss_projection_masks,
-                    "spatial_pairwise": self.loss_spatial_pairwise,
-                    "temporal_pairwise": self.loss_temporal_pairwise}
-        assert loss in loss_map, f"do you really want to compute {loss} loss?"
-        return loss_map[loss](outputs, targets, indices, num_masks)
-
     # -- driver ------------------------------------------------------------------------------------------
-    def _targets(self, targets, device):
-        # built once per forward() for all heads; a direct get_loss() call outside forward builds its own
-        if self._tg is None or self._tg_key is not targets:
-            need_sim = "spatial_pairwise" in self.losses or getattr(self.matcher, "cost_pairwise", 0) != 0
-            self._tg = VideoWeakTargets(targets, device, self.pairwise_color_thresh, need_sim=need_sim)
-            self._tg_key = targets
-        return self._tg
-
-    def _match(self, outputs, targets):
-        if isinstance(self.matcher, VideoHungarianMatcherProjPair):
-            self.matcher.last_status = None
-            idx = self.matcher(outputs, targets, prepared=self._targets(targets, outputs["pred_masks"].device))
-            if self.matcher.last_status is not None:
-                self._status.append(self.matcher.last_status)
-            return idx
-        return self.matcher(outputs, targets)
+    def _make_targets(self, targets, device):
+        need_sim = "spatial_pairwise" in self.losses or getattr(self.matcher, "cost_pairwise", 0) != 0
+        return VideoWeakTargets(targets, device, self.pairwise_color_thresh, need_sim=need_sim)
 
     def _check(self):
         """The call's one host sync: scipy's ValueErrors for the assignments, IndexError for a pair off the frame."""
@@ -444,43 +363,9 @@ class VideoSetCriterionProjSpatPairTempPair(nn.Module):
             raise IndexError("temporal_pairs holds a coordinate outside the (H, W) frame")
 
     def forward(self, outputs, targets):
-        self._tg = self._tg_key = None
-        self._status = []
-        self._gathered = {}
-        try:
-            outputs_without_aux = {k: v for k, v in outputs.items() if k != "aux_outputs"}
-            indices = self._match(outputs_without_aux, targets)
-            dev = next(iter(outputs.values())).device
-            n = sum(len(t["labels"]) for t in targets)
-            world = _dist_world()
-            if world:
-                nm = torch.as_tensor([n], dtype=torch.float, device=dev)
-                torch.distributed.all_reduce(nm)
-                num_masks = torch.clamp(nm / world, min=1)[0]      # stays on the device (no .item())
-            else:
-                num_masks = max(float(np.float32(n)), 1.0)
-            losses = {}
-            for loss in self.losses:
-                losses.update(self.get_loss(loss, outputs, targets, indices, num_masks))
-            for i, aux_outputs in enumerate(outputs.get("aux_outputs", [])):
-                indices = self._match(aux_outputs, targets)
-                for loss in self.losses:
-                    l_dict = self.get_loss(loss, aux_outputs, targets, indices, num_masks)
-                    losses.update({k + f"_{i}": v for k, v in l_dict.items()})
-            if self.check_matching:
-                self._check()
-            self._iter_host.step(self._iter)
-            return losses
-        finally:
-            self._tg = self._tg_key = None
-            self._status = []
-            self._gathered = {}
-
-    def __repr__(self):
-        head = "Criterion " + self.__class__.__name__
-        body = [f"matcher: {self.matcher.__repr__(_repr_indent=8)}", f"losses: {self.losses}",
-                f"weight_dict: {self.weight_dict}", f"num_classes: {self.num_classes}", f"eos_coef: {self.eos_coef}"]
-        return "\n".join([head] + [" " * 4 + line for line in body])
+        losses = super().forward(outputs, targets)
+        self._iter_host.step(self._iter)     # after the losses: the first call sees warm-up factor 0
+        return losses
 
 
 class VideoSetCriterionProjSpatPair(VideoSetCriterionProjSpatPairTempPair):

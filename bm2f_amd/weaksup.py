@@ -2,10 +2,12 @@
 batched Hungarian matching, the pairwise-affinity cost / loss, neighbour-similarity bits and the GPU target
 preparation that replaces the reference's per-image host loop with skimage.
 
-Every image-criterion op takes CUDA tensors and raises on anything else: there is no CPU path (the CPU restatement
-lives in ``oracle/weaksup_ref.py`` and is test infrastructure only).  The temporal-pair ops of the video criterion
-(``csrc/video_pairs.hip``: packing, the temporal pairwise sum, pair mining) also evaluate their definition in plain
-torch on CPU tensors, like ``inference.py``.
+The pairwise, LSAP and target-preparation ops here take CUDA tensors and raise on anything else: they have no CPU
+path (the CPU restatement lives in ``oracle/weaksup_ref.py`` and is test infrastructure only), so the image
+criterion's losses need HIP tensors.  Its matcher is the video matcher on one-frame clips and, like that one, evaluates
+its definition in plain torch (scipy for the assignment) on CPU tensors without calling these ops.  The temporal-pair
+ops of the video criterion (``csrc/video_pairs.hip``: packing, the temporal pairwise sum, pair mining) also evaluate
+their definition in plain torch on CPU tensors, like ``inference.py``.
 """
 from __future__ import annotations
 

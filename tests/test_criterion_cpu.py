@@ -108,6 +108,55 @@ def test_oracle_matcher_and_losses_vs_reference(gold):
             np.testing.assert_allclose(hd["pred_masks"].grad.numpy(), z[f"it{it}_gmasks{h}"], rtol=1e-4, atol=1e-9)
 
 
+@pytest.mark.parametrize("shared", [False, True])
+def test_image_matcher_cpu_vs_reference(gold, shared):
+    """HungarianMatcherProjPair on CPU tensors (the video matcher's torch path on one-frame clips) returns the
+    reference's indices for every iteration and head, called in the criterion's order."""
+    from bm2f_amd.criterion import HungarianMatcherProjPair
+    z = gold
+    targets = fixture_targets(z, shared=shared)
+    w_class, w_proj, w_pair = (float(v) for v in z["weights"])
+    n_aux = int(z["n_aux"])
+    matcher = HungarianMatcherProjPair(cost_class=w_class, cost_projection=w_proj, cost_pairwise=w_pair,
+                                       pairwise_size=3, pairwise_dilation=2, pairwise_color_thresh=0.3,
+                                       pairwise_warmup_iters=int(z["warmup"]))
+    for it in range(int(z["iters"])):
+        heads = _heads(z, it)
+        for h in [n_aux] + list(range(n_aux)):          # the criterion's matcher call order
+            idx = matcher(heads[h], targets)
+            assert len(idx) == len(targets)
+            for b, (i, j) in enumerate(idx):
+                assert np.array_equal(np.stack([i.numpy(), j.numpy()]), z[f"it{it}_idx{h}_{b}"]), (it, h, b)
+    assert float(matcher._iter) == int(z["iters"]) * (n_aux + 1)
+
+
+def test_matcher_status_is_reset_before_every_call():
+    """A matcher call that returns early (no targets) leaves ``last_status`` alone; the criterion must not take
+    the previous call's failed status for it."""
+    from bm2f_amd.criterion import HungarianMatcherProjPair, SetCriterionProjPair
+
+    class Stub(HungarianMatcherProjPair):
+        calls = 0
+
+        def forward(self, outputs, targets, prepared=None):
+            self.calls += 1
+            if self.calls == 1:
+                self.last_status = torch.tensor([3], dtype=torch.int32)     # invalid numeric entries
+            e = torch.empty(0, dtype=torch.int64)
+            return [(e, e) for _ in targets]
+
+    stub = Stub()
+    crit = SetCriterionProjPair(3, stub, {}, 0.1, 3, 2, 0.3, 10, ["labels"], False, 0, 3.0, 0.75)
+    assert crit.check_matching
+    outputs = {"pred_logits": torch.zeros(1, 2, 4), "pred_masks": torch.zeros(1, 2, 4, 4)}
+    targets = [{"labels": torch.zeros(0, dtype=torch.int64), "box_masks": torch.zeros(0, 4, 4),
+                "images_color_similarity": torch.zeros(0, 8, 4, 4)}]
+    with pytest.raises(ValueError, match="invalid numeric entries"):
+        crit(outputs, targets)
+    assert set(crit(outputs, targets)) == {"loss_ce"}      # the early return: nothing to report, nothing raised
+    assert stub.calls == 2
+
+
 def test_lsap_fixture_is_scipy():
     from scipy.optimize import linear_sum_assignment
     z = np.load(os.path.join(GOLD, "lsap.npz"))
