@@ -11,6 +11,9 @@ from .mask_criterion import HungarianMatcher, SetCriterion, VideoHungarianMatche
 from .video_criterion import (VideoHungarianMatcherProj, VideoHungarianMatcherProjPair,  # noqa: F401
                               VideoSetCriterionProj, VideoSetCriterionProjSpatPair,
                               VideoSetCriterionProjSpatPairTempPair)
+from .video_inference import VideoMaskFormerInference, pack_mask_bits, unpack_mask_bits  # noqa: F401
+from .video_targets import (feat_resize_pad, prepare_video_targets,  # noqa: F401
+                            prepare_video_weaksup_targets)
 from .msda import MSDeformAttn, MSDeformAttnFunction, ms_deform_attn_backward, ms_deform_attn_forward  # noqa: F401
 
 __version__ = "0.1.0"

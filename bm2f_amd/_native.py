@@ -104,6 +104,8 @@ _SIGNATURES = {
     "m2f_infer_semantic": [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p],
     "m2f_infer_panoptic_pass": [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p],
     "m2f_infer_instance": [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p],
+    "m2f_infer_video": [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],
+    "m2f_feat_resize_pad": [_p, _i, _l, _i, _i, _i, _i, _i, _i, _p, _p],
 }
 
 

@@ -371,7 +371,7 @@ int m2f_maxpool3s2_nhwc(int backward, const void* src, void* dst, uint8_t* windo
  * backward: 32 or 16, the heads of one image and key chunk on one XCD: 1 or 0), mattn_combine (forward chunk
  * combine: a thread per row part 0, a wave per row 1), mask_df_stage (mask-einsum feature
  * gradient: k-steps per LDS stage, 4 or 1), gemm_nt_cfg, x3_tn_nw, x3_tn_blocks,
- * x3_nt_cfg (GEMM tilings).  Every option changes
+ * x3_nt_cfg (GEMM tilings), infer_video_cap (m2f_infer_video's LDS budget in source texels).  Every option changes
  * the partition or kernel variant only; results agree to fp32 rounding (summation order may differ between
  * variants).  Process-wide; not synchronised with launches in flight on other threads.  Unknown names return
  * M2F_EINVAL. */
@@ -611,6 +611,30 @@ int m2f_infer_instance(const void* logits, int dtype, const int32_t* sel_idx, co
                        const int32_t* sizes, int batch, int num_queries, int max_sel, int in_h, int in_w, int pad_h,
                        int pad_w, int out_h, int out_w, int num_tiles, uint8_t* masks, float* partials, float* sums,
                        void* stream);
+
+/* The eval branch of VideoMaskFormer.forward (mask2former_video/video_maskformer_model.py:372-393) and the
+ * pixel pass of inference_video (:651-694) on clip 0: logits (Q, T, in_h, in_w) of `dtype`, read in place;
+ * slot_query (num_slots,) int32: the distinct selected queries, num_sel (device, may be NULL = all slots)
+ * how many of them are live.  The value of a pixel is the resize chain above with one image geometry for
+ * the whole clip: interpolate to (pad_h, pad_w), crop to (crop_h, crop_w), interpolate to (out_h, out_w)
+ * (skipped when equal), then > 0 (:666).  packed = 0: out (num_slots, T, out_h, out_w) uint8 0/1;
+ * packed = 1: out (num_slots, T, out_h, ceil(out_w / 32)) int32, bit x % 32 of word x / 32, tail bits
+ * zero.  Slots >= *num_sel are left untouched.  A workgroup stages its tile's source box in LDS when the
+ * box has at most `infer_video_cap` texels (m2f_set_option; default 1536, 0 = never, at most 12288) and
+ * reads global memory otherwise; both paths give identical bits.  out 4-byte aligned and crop <= pad, else
+ * M2F_EINVAL.  T, num_slots <= 65535, in_h * in_w and out_h * out_w < 2^31, else M2F_EUNSUPPORTED. */
+int m2f_infer_video(const void* logits, int dtype, const int32_t* slot_query, const int32_t* num_sel,
+                    int num_queries, int num_slots, int num_frames, int in_h, int in_w, int pad_h, int pad_w,
+                    int crop_h, int crop_w, int out_h, int out_w, int packed, void* out, void* stream);
+/* The DINO feature resize of prepare_weaksup_targets (video_maskformer_model.py:506-517): feats (planes,
+ * src_h, src_w) of `dtype` -> out (planes, out_h, out_w) fp32 = torch's bilinear F.interpolate
+ * (align_corners=False) of the features zero-padded bottom/right to (pad_h, pad_w), without building the
+ * padded copy: taps are clamped to the padded size, a tap at or beyond (src_h, src_w) contributes 0.  The
+ * source coordinate and tap weights are exact (integer arithmetic) and the four-tap blend is fp32, so the
+ * result is within fp32 rounding of the fp64 interpolation, and equal to torch's fp32 result bit for bit
+ * where torch's own weights are exact (integer ratios such as the stride-4 resize).  src <= pad, else M2F_EINVAL; plane sizes < 2^31, else M2F_EUNSUPPORTED. */
+int m2f_feat_resize_pad(const void* feats, int dtype, int64_t planes, int src_h, int src_w, int pad_h, int pad_w,
+                        int out_h, int out_w, float* out, void* stream);
 
 #ifdef __cplusplus
 }
