@@ -8,6 +8,7 @@ from . import _native  # noqa: F401
 from .inference import (MaskFormerInference, instance_inference, panoptic_inference,  # noqa: F401
                         semantic_inference)
 from .mask_criterion import HungarianMatcher, SetCriterion, VideoHungarianMatcher, VideoSetCriterion  # noqa: F401
+from .swin import D2SwinTransformer, SwinTransformer, window_attention  # noqa: F401
 from .video_criterion import (VideoHungarianMatcherProj, VideoHungarianMatcherProjPair,  # noqa: F401
                               VideoSetCriterionProj, VideoSetCriterionProjSpatPair,
                               VideoSetCriterionProjSpatPairTempPair)

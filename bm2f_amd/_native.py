@@ -106,6 +106,9 @@ _SIGNATURES = {
     "m2f_infer_instance": [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p],
     "m2f_infer_video": [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],
     "m2f_feat_resize_pad": [_p, _i, _l, _i, _i, _i, _i, _i, _i, _p, _p],
+    "m2f_window_attn_workspace": [_i, _i, _i, _i, _i, _p],
+    "m2f_window_attn_fwd": [_i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p],
+    "m2f_window_attn_bwd": [_i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _l, _p],
 }
 
 

@@ -1,7 +1,8 @@
 """Detectron2 surface the hot-path modules plug into.
 
 When detectron2 is importable its real ``configurable`` / ``Conv2d`` / ``ShapeSpec`` / ``get_norm`` and
-``SEM_SEG_HEADS_REGISTRY`` are used, so ``build_pixel_decoder`` (reference pixel_decoder/fpn.py:21-33) and
+``SEM_SEG_HEADS_REGISTRY`` / ``BACKBONE_REGISTRY`` are used, so ``build_pixel_decoder`` (reference
+pixel_decoder/fpn.py:21-33) and
 ``build_transformer_decoder`` (transformer_decoder/maskformer_transformer_decoder.py:22-27) find the
 modules exactly as they find the reference's.  The transformer-decoder registry is the reference's own
 ``TRANSFORMER_DECODER_REGISTRY`` object whenever its module
@@ -110,6 +111,13 @@ except Exception:  # noqa: BLE001
 
     SEM_SEG_HEADS_REGISTRY = Registry("SEM_SEG_HEADS")
 
+# detectron2's own backbone registry and base class when it has them, else local ones of the same role
+try:  # pragma: no cover - detectron2 is absent in this image
+    from detectron2.modeling import BACKBONE_REGISTRY, Backbone  # type: ignore
+except Exception:  # noqa: BLE001
+    BACKBONE_REGISTRY = Registry("BACKBONE")
+    Backbone = nn.Module
+
 REFERENCE_TD_MODULE = "mask2former.modeling.transformer_decoder.maskformer_transformer_decoder"
 
 # Same name and role as mask2former/modeling/transformer_decoder/maskformer_transformer_decoder.py:16; used
@@ -151,9 +159,11 @@ def install():
     """(Re)register the bm2f classes into the registries visible now: call after importing the reference's
     modules in an order where bm2f was imported first."""
     from .pixel_decoder import MSDeformAttnPixelDecoder
+    from .swin import D2SwinTransformer
     from .transformer_decoder import MultiScaleMaskedTransformerDecoder
     from .video_decoder import VideoMultiScaleMaskedTransformerDecoder
     _register_replacing(SEM_SEG_HEADS_REGISTRY, MSDeformAttnPixelDecoder)
+    _register_replacing(BACKBONE_REGISTRY, D2SwinTransformer)
     for cls in (MultiScaleMaskedTransformerDecoder, VideoMultiScaleMaskedTransformerDecoder):
         _register_replacing(transformer_decoder_registry(), cls)
         if transformer_decoder_registry() is not _LOCAL_TD_REGISTRY:
@@ -190,5 +200,6 @@ def c2_xavier_fill(module: nn.Module) -> None:
 
 
 __all__ = ["Registry", "configurable", "ShapeSpec", "Conv2d", "get_norm", "SEM_SEG_HEADS_REGISTRY",
+           "BACKBONE_REGISTRY", "Backbone",
            "TRANSFORMER_DECODER_REGISTRY", "transformer_decoder_registry", "register", "install",
            "build_pixel_decoder", "build_transformer_decoder", "c2_xavier_fill", "HAVE_DETECTRON2"]

@@ -636,6 +636,27 @@ int m2f_infer_video(const void* logits, int dtype, const int32_t* slot_query, co
 int m2f_feat_resize_pad(const void* feats, int dtype, int64_t planes, int src_h, int src_w, int pad_h, int pad_w,
                         int out_h, int out_w, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Shifted-window attention of the Swin block (reference backbone/swin.py:131-171, :257-284): what lies
+ * between the qkv linear and the proj linear, with the cyclic shift, the window partition, the
+ * relative-position bias gather and the shift mask (-100 where the nine-region labels differ) computed
+ * from addresses inside the kernels.
+ *   qkv    (batch, hp, wp, 3 * heads * head_dim) of `dtype` (M2F_F32 / M2F_F16 / M2F_BF16), [q | k | v]
+ *   table  ((2 ws - 1)^2, heads) fp32 relative-position bias table
+ *   out    (batch, hp, wp, heads * head_dim) of `dtype`, unshifted and unpartitioned
+ *   lse    (batch, heads, hp * wp) fp32 log-sum-exp of every query row (all the backward needs saved)
+ * hp and wp are multiples of ws, 0 <= shift < ws (else M2F_EINVAL); 2 <= ws <= 12 and head_dim == 32
+ * (else M2F_EUNSUPPORTED).  qkv, out, dout and dqkv are 16-byte aligned and contiguous.
+ * The backward writes every element of dqkv (same shape as qkv) with plain stores and dtable
+ * ((2 ws - 1)^2, heads) fp32 as a fixed-order sum of per-workgroup partials held in `workspace`
+ * (m2f_window_attn_workspace bytes): no atomics, no memset, bitwise repeatable. */
+int m2f_window_attn_workspace(int batch, int heads, int hp, int wp, int ws, int64_t* bytes);
+int m2f_window_attn_fwd(int dtype, const void* qkv, const float* table, int batch, int heads, int head_dim, int hp,
+                        int wp, int ws, int shift, float scale, void* out, float* lse, void* stream);
+int m2f_window_attn_bwd(int dtype, const void* qkv, const float* table, const void* dout, const float* lse,
+                        int batch, int heads, int head_dim, int hp, int wp, int ws, int shift, float scale,
+                        void* dqkv, float* dtable, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
