@@ -8,6 +8,8 @@ from . import _native  # noqa: F401
 from .inference import (MaskFormerInference, instance_inference, panoptic_inference,  # noqa: F401
                         semantic_inference)
 from .mask_criterion import HungarianMatcher, SetCriterion, VideoHungarianMatcher, VideoSetCriterion  # noqa: F401
+from .evaluation import instances_to_coco_json, instances_to_coco_json_video  # noqa: F401
+from .rle import counts_to_string, rle_area, rle_decode, rle_encode, string_to_counts  # noqa: F401
 from .swin import D2SwinTransformer, SwinTransformer, window_attention  # noqa: F401
 from .video_criterion import (VideoHungarianMatcherProj, VideoHungarianMatcherProjPair,  # noqa: F401
                               VideoSetCriterionProj, VideoSetCriterionProjSpatPair,

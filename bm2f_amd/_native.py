@@ -109,6 +109,10 @@ _SIGNATURES = {
     "m2f_window_attn_workspace": [_i, _i, _i, _i, _i, _p],
     "m2f_window_attn_fwd": [_i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p],
     "m2f_window_attn_bwd": [_i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _l, _p],
+    "m2f_rle_col_counts": [_p, _i, _p, _i, _i, _i, _i, _l, _l, _p, _p],
+    "m2f_rle_positions": [_p, _i, _p, _i, _i, _i, _i, _l, _l, _p, _p, _l, _p],
+    "m2f_rle_deltas": [_p, _p, _i, _i, _l, _p, _p, _p],
+    "m2f_rle_chars": [_p, _p, _p, _l, _p, _l, _p],
 }
 
 

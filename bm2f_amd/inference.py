@@ -26,6 +26,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _native
+from .rle import _BYTES, _encode_device, rle_encode
 
 _CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 _MAX_Q = 256
@@ -229,9 +230,11 @@ def _thing_filter(labels, thing_classes):
     return torch.isin(labels, things)
 
 
-def _instance_hip(mask_cls, mask_pred, padded_size, geo, num_classes, topk, thing_classes=None):
+def _instance_hip(mask_cls, mask_pred, padded_size, geo, num_classes, topk, thing_classes=None, rle=False):
     """The thing filter of the panoptic setting (:604-611) is applied to the (topk,) lists before the float masks
-    are gathered, so only the kept masks are ever expanded."""
+    are gathered, so only the kept masks are ever expanded.  With ``rle`` the uint8 masks are not expanded at all:
+    every live slot's (Ho_b, Wo_b) crop is run-length encoded in place (``csrc/rle.hip``, byte form) and the
+    entries index the encoded slots."""
     masks, sizes, Ho, Wo = _prep(mask_pred, geo)
     B, Q, h, w = masks.shape
     Hp, Wp = _pair(padded_size)
@@ -256,7 +259,15 @@ def _instance_hip(mask_cls, mask_pred, padded_size, geo, num_classes, topk, thin
             keep = _thing_filter(lab, thing_classes)
             slot, sc, lab = slot[keep], sc[keep], lab[keep]
         sm = sums[b, slot]
-        results.append({"pred_masks": binary[b, slot, :g[2], :g[3]].float(),
+        if rle:
+            live = torch.arange(S, device=masks.device)
+            live = torch.where(live < n_sel[b], live, torch.zeros_like(live)).to(torch.int32)
+            enc, slot_h = _encode_device(binary[b, :, :g[2], :g[3]], _BYTES, g[3], plane_index=live, num_masks=S,
+                                         extra=slot)
+            mask_entry = {"pred_masks_rle": [enc[i] for i in slot_h.tolist()]}
+        else:
+            mask_entry = {"pred_masks": binary[b, slot, :g[2], :g[3]].float()}
+        results.append({**mask_entry,
                         "scores": sc * (sm[:, 0] / (sm[:, 1] + 1e-6)),
                         "pred_classes": lab, "image_size": (g[2], g[3])})
     return results
@@ -292,7 +303,7 @@ def _finish_instances(r, thing_classes):
     if thing_classes is not None:
         keep = _thing_filter(r["pred_classes"], thing_classes)
         r = {k: (v[keep] if torch.is_tensor(v) else v) for k, v in r.items()}
-    r["pred_boxes"] = torch.zeros(r["pred_masks"].size(0), 4)
+    r["pred_boxes"] = torch.zeros(r["scores"].size(0), 4)
     return r
 
 
@@ -366,11 +377,14 @@ class MaskFormerInference(nn.Module):
                    sem_seg_postprocess_before_inference=t.SEM_SEG_POSTPROCESSING_BEFORE_INFERENCE,
                    test_topk_per_image=cfg.TEST.DETECTIONS_PER_IMAGE)
 
-    def forward(self, outputs, padded_size, image_sizes, output_sizes=None, semantic_labels=False):
+    def forward(self, outputs, padded_size, image_sizes, output_sizes=None, semantic_labels=False,
+                instance_rle=False):
         """outputs: {"pred_logits": (B, Q, K+1), "pred_masks": (B, Q, h, w)}; padded_size: (Hp, Wp) of the padded
         batch; image_sizes: (Hc, Wc) per image; output_sizes: (height, width) per image (default: the image size).
         Returns one dict per image keyed as the reference's processed_results.  With ``semantic_labels`` the
-        semantic head returns ``"sem_seg_labels"`` (int16 argmax map) instead of the (K, H, W) scores."""
+        semantic head returns ``"sem_seg_labels"`` (int16 argmax map) instead of the (K, H, W) scores.  With
+        ``instance_rle`` each image's ``"instances"`` holds ``pred_masks_rle``, a list of COCO RLE dicts
+        (``bm2f_amd.rle``) at that image's output size, in place of the float ``pred_masks``."""
         mask_cls, mask_pred = outputs["pred_logits"], outputs["pred_masks"]
         B, Q = mask_pred.shape[:2]
         if mask_cls.shape[-1] != self.num_classes + 1:
@@ -417,11 +431,14 @@ class MaskFormerInference(nn.Module):
             ins_things = things if self.panoptic_on else None
             if hip:
                 ins = _instance_hip(mask_cls, mask_pred, padded_size, geo, self.num_classes, self.test_topk_per_image,
-                                    ins_things)
+                                    ins_things, rle=instance_rle)
                 ins_things = None   # already applied
             else:
                 ins = [_instance_cpu(mask_cls[b], full[b], self.num_classes, self.test_topk_per_image)
                        for b in range(B)]
             for b in range(B):
-                results[b]["instances"] = _finish_instances(ins[b], ins_things)
+                r = _finish_instances(ins[b], ins_things)
+                if instance_rle and not hip:
+                    r["pred_masks_rle"] = rle_encode(r.pop("pred_masks") > 0)
+                results[b]["instances"] = r
         return results

@@ -28,6 +28,7 @@ from torch import nn
 
 from . import _native
 from .inference import _code, _geometry, _pair, _stream, full_resolution_logits
+from .rle import _BITS, _encode_device, rle_encode
 
 
 def pack_mask_bits(masks: torch.Tensor) -> torch.Tensor:
@@ -45,6 +46,14 @@ def unpack_mask_bits(words: torch.Tensor, width: int) -> torch.Tensor:
     return bits.flatten(-2)[..., :width].bool()
 
 
+def _select_slots(Q, S, qidx):
+    """The distinct selected queries take the first slots: -> entry -> slot, slot -> query (S,) int32, live slots."""
+    mark = torch.zeros(Q, dtype=torch.bool, device=qidx.device).scatter_(0, qidx, True)
+    order = torch.sort((~mark).to(torch.uint8), stable=True).indices       # selected queries first
+    slot = torch.sort(order).indices.gather(0, qidx)                        # entry -> slot
+    return slot, order[:S].to(torch.int32).contiguous(), mark.sum().to(torch.int32).reshape(1)
+
+
 def _video_masks_hip(mask_pred, qidx, scores, labels, padded_size, geo, packed):
     """-> host (scores, labels, slots, masks (S, T, Ho, Wo) bool or (S, T, Ho, words) int32): one copy."""
     masks = mask_pred.detach().contiguous()
@@ -54,11 +63,7 @@ def _video_masks_hip(mask_pred, qidx, scores, labels, padded_size, geo, packed):
     dev = masks.device
     k = qidx.numel()
     S = min(Q, k)
-    mark = torch.zeros(Q, dtype=torch.bool, device=dev).scatter_(0, qidx, True)
-    order = torch.sort((~mark).to(torch.uint8), stable=True).indices       # selected queries first
-    slot = torch.sort(order).indices.gather(0, qidx)                        # entry -> slot
-    sel = order[:S].to(torch.int32).contiguous()
-    n_sel = mark.sum().to(torch.int32).reshape(1)
+    slot, sel, n_sel = _select_slots(Q, S, qidx)
     # one int32 buffer: [masks | scores (fp32 bits) | labels | slots]
     row = (Wo + 31) // 32 if packed else Wo
     body = S * T * Ho * row
@@ -76,6 +81,31 @@ def _video_masks_hip(mask_pred, qidx, scores, labels, padded_size, geo, packed):
     else:
         out = host[:words].view(torch.uint8)[:body].view(S, T, Ho, Wo).view(torch.bool)
     return tail[:k].view(torch.float32), tail[k:2 * k], tail[2 * k:].tolist(), out
+
+
+def _video_rle_hip(mask_pred, qidx, scores, labels, padded_size, geo):
+    """-> host (scores, labels, slots, rles): rles[s] are the T RLE dicts of slot s.  The packed masks stay on the
+    device and are encoded there (``csrc/rle.hip``); scores, labels and slots ride with the encoder's first copy."""
+    masks = mask_pred.detach().contiguous()
+    Q, T, h, w = masks.shape
+    Hp, Wp = _pair(padded_size)
+    Hc, Wc, Ho, Wo = geo
+    dev = masks.device
+    k = qidx.numel()
+    S = min(Q, k)
+    slot, sel, n_sel = _select_slots(Q, S, qidx)
+    bits = torch.empty((S * T, Ho, (Wo + 31) // 32), dtype=torch.int32, device=dev)
+    _native.call("m2f_infer_video", masks.data_ptr(), _code(masks), sel.data_ptr(), n_sel.data_ptr(), Q, S, T, h, w,
+                 Hp, Wp, Hc, Wc, Ho, Wo, 1, bits.data_ptr(), _stream(masks))
+    # slots >= n_sel were not written: they are encoded from slot 0 and never indexed
+    live = torch.arange(S, device=dev)
+    live = torch.where(live < n_sel, live, torch.zeros_like(live))
+    planes = (live[:, None] * T + torch.arange(T, device=dev)).flatten().to(torch.int32)
+    extra = torch.cat([scores.float().view(torch.int32), labels.to(torch.int32), slot.to(torch.int32)])
+    rles, tail = _encode_device(bits, _BITS, Wo, plane_index=planes, num_masks=S * T, extra=extra)
+    tail = tail.to(torch.int32)
+    return (tail[:k].view(torch.float32), tail[k:2 * k], tail[2 * k:].tolist(),
+            [rles[s * T:(s + 1) * T] for s in range(S)])
 
 
 def _video_masks_cpu(mask_pred, qidx, padded_size, geo, packed):
@@ -103,12 +133,16 @@ class VideoMaskFormerInference(nn.Module):
         return cls(cfg.MODEL.SEM_SEG_HEAD.NUM_CLASSES)
 
     @torch.no_grad()
-    def forward(self, outputs, padded_size, image_size, output_size=None, packed=False):
+    def forward(self, outputs, padded_size, image_size, output_size=None, packed=False, rle=False):
         """outputs: {"pred_logits": (1|B, Q, K+1), "pred_masks": (1|B, Q, T, h, w)}; padded_size (Hp, Wp) of the
         padded frames, image_size (Hc, Wc) without padding, output_size (height, width) (default: the image size).
         Returns the reference's dict: ``image_size`` (the output size), ``pred_scores``, ``pred_labels`` and
         ``pred_masks``, a list of (T, Ho, Wo) bool CPU tensors; with ``packed`` they are (T, Ho, ceil(Wo / 32)) int32
-        words (see :func:`unpack_mask_bits`) and the dict also holds ``"packed": True``."""
+        words (see :func:`unpack_mask_bits`) and the dict also holds ``"packed": True``.  With ``rle`` they are lists
+        of T COCO RLE dicts (``bm2f_amd.rle``), encoded on the device from the packed masks, and the dict holds
+        ``"rle": True``; entries that share a query share one list."""
+        if rle and packed:
+            raise ValueError("rle=True returns encoded masks; it cannot be combined with packed=True")
         mask_cls, mask_pred = outputs["pred_logits"][0], outputs["pred_masks"][0]
         if mask_pred.dim() != 4:
             raise ValueError("pred_masks must be (B, Q, T, h, w)")
@@ -118,17 +152,25 @@ class VideoMaskFormerInference(nn.Module):
         result = {"image_size": (geo[2], geo[3]), "pred_scores": [], "pred_labels": [], "pred_masks": []}
         if packed:
             result["packed"] = True
+        if rle:
+            result["rle"] = True
         Q, K = mask_pred.shape[0], self.num_classes
         if Q == 0:
             return result
         scores = F.softmax(mask_cls.float(), dim=-1)[:, :-1]
         s, idx = scores.flatten(0, 1).topk(min(self.test_topk_per_video, Q * K), sorted=False)   # :656
         labels, qidx = idx % K, idx // K
-        if mask_pred.device.type == "cuda":
+        if rle and mask_pred.device.type == "cuda":
+            s, labels, slot, masks = _video_rle_hip(mask_pred, qidx, s, labels, padded_size, geo)
+        elif mask_pred.device.type == "cuda":
             s, labels, slot, masks = _video_masks_hip(mask_pred, qidx, s, labels, padded_size, geo, packed)
         else:
             masks = _video_masks_cpu(mask_pred, qidx, padded_size, geo, packed)
             slot = range(qidx.numel())
+            if rle:
+                T = masks.shape[1]
+                flat = rle_encode(masks)
+                masks = [flat[i * T:(i + 1) * T] for i in slot]
         result["pred_scores"] = s.tolist()
         result["pred_labels"] = labels.tolist()
         result["pred_masks"] = [masks[i] for i in slot]

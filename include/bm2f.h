@@ -657,6 +657,50 @@ int m2f_window_attn_bwd(int dtype, const void* qkv, const float* table, const vo
                         int batch, int heads, int head_dim, int hp, int wp, int ws, int shift, float scale,
                         void* dqkv, float* dtable, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * COCO run-length encoding of binary masks on the device (the form the reference's evaluators get from
+ * pycocotools.mask.encode, mask2former_video/data_video/ytvis_eval.py:256-293), restated here:
+ *   a mask (H, W) is read column-major, pixel p = x * H + y; t_0 < ... < t_{k-1} are the positions with
+ *   pixel(p) != pixel(p - 1), pixel(-1) = 0; counts = [t_0, t_1 - t_0, ..., H * W - t_{k-1}] (k + 1 values,
+ *   counts[0] == 0 when pixel 0 is set); count i goes out as delta = counts[i] - (i > 2 ? counts[i - 2] : 0)
+ *   in 5-bit groups, low group first, each group + 48 with bit 0x20 set while more groups follow (at most
+ *   7 characters).
+ * `num_masks` masks of one size are read in place from `masks`, form M2F_RLE_BITS or M2F_RLE_BYTES:
+ *   bits   int32 words, bit x % 32 of word x / 32 (what m2f_infer_video writes with packed = 1); a set tail
+ *          bit beyond `width` is never read; 4-byte aligned
+ *   bytes  uint8 / bool, non-zero = set
+ * with `row_stride` and `plane_stride` in elements (words or bytes).  Mask m is source plane
+ * plane_index[m] clamped to [0, src_planes) when plane_index (device int32) is given, else plane m; the
+ * source then holds src_planes planes (>= num_masks without a table).
+ * Four stages, each a launch on `stream`; the two scans between them are the caller's (an inclusive
+ * int64 prefix sum, e.g. torch.cumsum) and the caller reads col_start[M * W] to size `positions`:
+ *   m2f_rle_col_counts   counts (M, W) int32: transitions in column x of mask m, the one between the column's
+ *                        first pixel and the previous column's last pixel (virtual 0 before column 0) included
+ *   m2f_rle_positions    col_start (M * W + 1) int64 = exclusive scan of counts.  positions (R + M) int32,
+ *                        R = col_start[M * W]: mask m owns [col_start[m * W] + m, col_start[(m + 1) * W] + m]:
+ *                        its t_j in order, then H * W.  A slot at or beyond `capacity` is never written.
+ *   m2f_rle_deltas       per count g < total = R + M: delta[g] int32 and nchar[g] uint8 (1..7)
+ *   m2f_rle_chars        char_end (total) int64 = inclusive scan of nchar; the characters of count g go to
+ *                        out[char_end[g] - nchar[g] ...]; mask m's string is out[e(s_m - 1) : e(s_{m+1} - 1)]
+ *                        with s_m = col_start[m * W] + m, e = char_end and e(-1) = 0.  A byte at or beyond
+ *                        `capacity` is never written.
+ * Every offset comes from a scan: no atomics, no dependence on workgroup order, identical bytes from run to
+ * run, and no per-mask run capacity.  Null pointers, non-positive sizes, H * W >= 2^31, a row stride
+ * smaller than the row or a plane stride smaller than H rows give M2F_EINVAL; num_masks > 65535 gives
+ * M2F_EUNSUPPORTED; all before any HIP call.
+ * ------------------------------------------------------------------------------------------- */
+enum { M2F_RLE_BITS = 0, M2F_RLE_BYTES = 1 };
+int m2f_rle_col_counts(const void* masks, int form, const int32_t* plane_index, int src_planes, int num_masks,
+                       int height, int width, int64_t row_stride, int64_t plane_stride, int32_t* counts,
+                       void* stream);
+int m2f_rle_positions(const void* masks, int form, const int32_t* plane_index, int src_planes, int num_masks,
+                      int height, int width, int64_t row_stride, int64_t plane_stride, const int64_t* col_start,
+                      int32_t* positions, int64_t capacity, void* stream);
+int m2f_rle_deltas(const int32_t* positions, const int64_t* col_start, int num_masks, int width, int64_t total,
+                   int32_t* delta, uint8_t* nchar, void* stream);
+int m2f_rle_chars(const int32_t* delta, const uint8_t* nchar, const int64_t* char_end, int64_t total, uint8_t* out,
+                  int64_t capacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
