@@ -22,7 +22,11 @@
 // 32*177*4 = 22656, tap tables 1440: 79392 at KT = 8, two workgroups per CU.
 //
 // Non-finite logits: the first-maximum scans compare with > as written, so a pixel whose scores are all NaN gets
-// label -1 (labels mode) or keeps the first kept query (panoptic), where torch.argmax returns the NaN's index.
+// label -1 (labels mode) or keeps the first kept query (panoptic), where torch.argmax returns the NaN's index
+// (the first one, so the panoptic head equals the CPU path and the labels differ from its 0).  The score planes
+// are NaN at such a pixel.  The instance head leaves a NaN pixel out of the mask and of the score (`v > 0` is
+// false), where the reference's mask score turns NaN.  +-inf logits give sigmoid exactly 1 / 0 in every head.
+// test_inference_sweep_gpu.py pins all of this.
 #include "bm2f.h"
 #include "common.h"
 #include "resize_device.h"

@@ -114,7 +114,7 @@ def fp64_eval(cls, full, K):
     keep = labels.ne(K) & (scores > OBJECT_MASK_THRESHOLD)
     kidx = keep.nonzero().flatten()
     sig = full.sigmoid()
-    amax = full.abs().max()
+    amax = full.abs()[full.isfinite()].max()                            # infinite logits do not set the scale
     near_zero = full.abs() < REL * amax                                  # (Q, H, W): `> 0` / `>= 0.5` may flip
     sem = torch.einsum("qc,qhw->chw", probs[:, :-1], sig)
     top2 = sem.topk(2, dim=0)
