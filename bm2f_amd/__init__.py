@@ -9,6 +9,7 @@ from .inference import (MaskFormerInference, instance_inference, panoptic_infere
                         semantic_inference)
 from .mask_criterion import HungarianMatcher, SetCriterion, VideoHungarianMatcher, VideoSetCriterion  # noqa: F401
 from .evaluation import instances_to_coco_json, instances_to_coco_json_video  # noqa: F401
+from .mask_iou import mask_iou, mask_pair_counts, rle_to_bits  # noqa: F401
 from .rle import counts_to_string, rle_area, rle_decode, rle_encode, string_to_counts  # noqa: F401
 from .swin import D2SwinTransformer, SwinTransformer, window_attention  # noqa: F401
 from .video_criterion import (VideoHungarianMatcherProj, VideoHungarianMatcherProjPair,  # noqa: F401
@@ -17,6 +18,8 @@ from .video_criterion import (VideoHungarianMatcherProj, VideoHungarianMatcherPr
 from .video_inference import VideoMaskFormerInference, pack_mask_bits, unpack_mask_bits  # noqa: F401
 from .video_targets import (feat_resize_pad, prepare_video_targets,  # noqa: F401
                             prepare_video_weaksup_targets)
+from .ytvis_eval import (YTVISEvalResult, YTVISEvaluator, YTVISGroundTruth, YTVISParams,  # noqa: F401
+                         evaluate_ytvis)
 from .msda import MSDeformAttn, MSDeformAttnFunction, ms_deform_attn_backward, ms_deform_attn_forward  # noqa: F401
 
 __version__ = "0.1.0"

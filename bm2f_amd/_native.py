@@ -113,6 +113,10 @@ _SIGNATURES = {
     "m2f_rle_positions": [_p, _i, _p, _i, _i, _i, _i, _l, _l, _p, _p, _l, _p],
     "m2f_rle_deltas": [_p, _p, _i, _i, _l, _p, _p, _p],
     "m2f_rle_chars": [_p, _p, _p, _l, _p, _l, _p],
+    "m2f_rle_decode_bits": [_p, _l, _p, _i, _i, _i, _p, _p],
+    "m2f_bits_pair_tiles": [_p, _p, _p],
+    "m2f_bits_pair_workspace": [_i, _i, _i, _i, _i, _p],
+    "m2f_bits_pair_counts": [_p, _i, _l, _p, _i, _l, _i, _i, _i, _p, _p, _p, _p, _l, _p],
 }
 
 

@@ -2,7 +2,8 @@
 (``instances_to_coco_json_video``, mask2former_video/data_video/ytvis_eval.py:256-293, and the COCO instance
 results detectron2 writes for mask2former/evaluation/instance_evaluation.py).  Masks go out as COCO RLE
 (``bm2f_amd.rle``); outputs the heads already encoded (``rle=True`` / ``instance_rle=True``) pass through, bool,
-float and packed masks are encoded here with :func:`rle_encode`.  Metrics are not computed here."""
+float and packed masks are encoded here with :func:`rle_encode`.  The video metrics are computed in
+``bm2f_amd.ytvis_eval``."""
 from __future__ import annotations
 
 import torch

@@ -54,8 +54,9 @@ def _select_slots(Q, S, qidx):
     return slot, order[:S].to(torch.int32).contiguous(), mark.sum().to(torch.int32).reshape(1)
 
 
-def _video_masks_hip(mask_pred, qidx, scores, labels, padded_size, geo, packed):
-    """-> host (scores, labels, slots, masks (S, T, Ho, Wo) bool or (S, T, Ho, words) int32): one copy."""
+def _video_masks_hip(mask_pred, qidx, scores, labels, padded_size, geo, packed, keep_bits=False):
+    """-> host (scores, labels, slots, masks (S, T, Ho, Wo) bool or (S, T, Ho, words) int32): one copy; and the
+    device bit planes (k, T, Ho, words) of the entries with ``keep_bits`` (else None)."""
     masks = mask_pred.detach().contiguous()
     Q, T, h, w = masks.shape
     Hp, Wp = _pair(padded_size)
@@ -74,18 +75,28 @@ def _video_masks_hip(mask_pred, qidx, scores, labels, padded_size, geo, packed):
     buf[words + 2 * k:] = slot.to(torch.int32)
     _native.call("m2f_infer_video", masks.data_ptr(), _code(masks), sel.data_ptr(), n_sel.data_ptr(), Q, S, T, h, w,
                  Hp, Wp, Hc, Wc, Ho, Wo, int(packed), buf.data_ptr(), _stream(masks))
+    bits = None
+    if keep_bits and packed:
+        bits = buf[:body].view(S, T, Ho, row)
+    elif keep_bits:                                                         # the byte form holds no planes: a second launch
+        bits = torch.empty((S, T, Ho, (Wo + 31) // 32), dtype=torch.int32, device=dev)
+        _native.call("m2f_infer_video", masks.data_ptr(), _code(masks), sel.data_ptr(), n_sel.data_ptr(), Q, S, T,
+                     h, w, Hp, Wp, Hc, Wc, Ho, Wo, 1, bits.data_ptr(), _stream(masks))
     host = buf.cpu()                                                        # the head's one synchronisation
     tail = host[words:]
     if packed:
         out = host[:body].view(S, T, Ho, row)
     else:
         out = host[:words].view(torch.uint8)[:body].view(S, T, Ho, Wo).view(torch.bool)
-    return tail[:k].view(torch.float32), tail[k:2 * k], tail[2 * k:].tolist(), out
+    if bits is not None:
+        bits = bits[slot]                                                   # entries that share a query share a slot
+    return tail[:k].view(torch.float32), tail[k:2 * k], tail[2 * k:].tolist(), out, bits
 
 
-def _video_rle_hip(mask_pred, qidx, scores, labels, padded_size, geo):
+def _video_rle_hip(mask_pred, qidx, scores, labels, padded_size, geo, keep_bits=False):
     """-> host (scores, labels, slots, rles): rles[s] are the T RLE dicts of slot s.  The packed masks stay on the
-    device and are encoded there (``csrc/rle.hip``); scores, labels and slots ride with the encoder's first copy."""
+    device and are encoded there (``csrc/rle.hip``); scores, labels and slots ride with the encoder's first copy.
+    With ``keep_bits`` the fifth value is the device bit planes (k, T, Ho, words) of the entries (else None)."""
     masks = mask_pred.detach().contiguous()
     Q, T, h, w = masks.shape
     Hp, Wp = _pair(padded_size)
@@ -105,7 +116,7 @@ def _video_rle_hip(mask_pred, qidx, scores, labels, padded_size, geo):
     rles, tail = _encode_device(bits, _BITS, Wo, plane_index=planes, num_masks=S * T, extra=extra)
     tail = tail.to(torch.int32)
     return (tail[:k].view(torch.float32), tail[k:2 * k], tail[2 * k:].tolist(),
-            [rles[s * T:(s + 1) * T] for s in range(S)])
+            [rles[s * T:(s + 1) * T] for s in range(S)], bits.view(S, T, Ho, -1)[slot] if keep_bits else None)
 
 
 def _video_masks_cpu(mask_pred, qidx, padded_size, geo, packed):
@@ -133,14 +144,16 @@ class VideoMaskFormerInference(nn.Module):
         return cls(cfg.MODEL.SEM_SEG_HEAD.NUM_CLASSES)
 
     @torch.no_grad()
-    def forward(self, outputs, padded_size, image_size, output_size=None, packed=False, rle=False):
+    def forward(self, outputs, padded_size, image_size, output_size=None, packed=False, rle=False, keep_bits=False):
         """outputs: {"pred_logits": (1|B, Q, K+1), "pred_masks": (1|B, Q, T, h, w)}; padded_size (Hp, Wp) of the
         padded frames, image_size (Hc, Wc) without padding, output_size (height, width) (default: the image size).
         Returns the reference's dict: ``image_size`` (the output size), ``pred_scores``, ``pred_labels`` and
         ``pred_masks``, a list of (T, Ho, Wo) bool CPU tensors; with ``packed`` they are (T, Ho, ceil(Wo / 32)) int32
         words (see :func:`unpack_mask_bits`) and the dict also holds ``"packed": True``.  With ``rle`` they are lists
         of T COCO RLE dicts (``bm2f_amd.rle``), encoded on the device from the packed masks, and the dict holds
-        ``"rle": True``; entries that share a query share one list."""
+        ``"rle": True``; entries that share a query share one list.  With ``keep_bits`` the dict also holds
+        ``"pred_bits"``, the (k, T, Ho, ceil(Wo / 32)) int32 bit planes of the entries on the device of the inputs
+        (what ``bm2f_amd.mask_iou`` and :class:`bm2f_amd.ytvis_eval.YTVISEvaluator` read without a new upload)."""
         if rle and packed:
             raise ValueError("rle=True returns encoded masks; it cannot be combined with packed=True")
         mask_cls, mask_pred = outputs["pred_logits"][0], outputs["pred_masks"][0]
@@ -161,12 +174,14 @@ class VideoMaskFormerInference(nn.Module):
         s, idx = scores.flatten(0, 1).topk(min(self.test_topk_per_video, Q * K), sorted=False)   # :656
         labels, qidx = idx % K, idx // K
         if rle and mask_pred.device.type == "cuda":
-            s, labels, slot, masks = _video_rle_hip(mask_pred, qidx, s, labels, padded_size, geo)
+            s, labels, slot, masks, bits = _video_rle_hip(mask_pred, qidx, s, labels, padded_size, geo, keep_bits)
         elif mask_pred.device.type == "cuda":
-            s, labels, slot, masks = _video_masks_hip(mask_pred, qidx, s, labels, padded_size, geo, packed)
+            s, labels, slot, masks, bits = _video_masks_hip(mask_pred, qidx, s, labels, padded_size, geo, packed,
+                                                            keep_bits)
         else:
             masks = _video_masks_cpu(mask_pred, qidx, padded_size, geo, packed)
             slot = range(qidx.numel())
+            bits = (masks if packed else pack_mask_bits(masks)) if keep_bits else None
             if rle:
                 T = masks.shape[1]
                 flat = rle_encode(masks)
@@ -174,4 +189,6 @@ class VideoMaskFormerInference(nn.Module):
         result["pred_scores"] = s.tolist()
         result["pred_labels"] = labels.tolist()
         result["pred_masks"] = [masks[i] for i in slot]
+        if keep_bits:
+            result["pred_bits"] = bits
         return result

@@ -701,6 +701,46 @@ int m2f_rle_deltas(const int32_t* positions, const int64_t* col_start, int num_m
 int m2f_rle_chars(const int32_t* delta, const uint8_t* nchar, const int64_t* char_end, int64_t total, uint8_t* out,
                   int64_t capacity, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mask IoU of instance sequences on bit planes: what the reference's video evaluator gets from
+ * pycocotools.mask.merge / area per (detection, ground truth, frame)
+ * (mask2former_video/data_video/datasets/ytvis_api/ytvoseval.py:176-222).
+ * A plane is (H, words) int32, words = ceil(W / 32), bit x % 32 of word x / 32 (M2F_RLE_BITS above).
+ *
+ *   m2f_rle_decode_bits   the reverse of the encoder.  positions (total) int32 holds, mask after mask, the
+ *                         cumulative run ends of the masks (counts summed up: the last one is H * W) in the
+ *                         column-major order p = x * H + y; mask m owns positions[offsets[m] : offsets[m + 1]],
+ *                         offsets (M + 1) int64 (clamped to [0, total] by the kernel).  Pixel p is set when an
+ *                         odd number of run ends is <= p, so equal ends (zero counts) are allowed and a mask
+ *                         with no ends is all zero.  out (M, H, words) int32: every word is written once with
+ *                         a plain store, tail bits zero; no memset, no atomics, the same bytes on every run.
+ *                         The ends must be non-decreasing inside a mask (the caller's check); unsorted ends
+ *                         give unspecified bits and no out-of-range access.
+ *   m2f_bits_pair_counts  a (Da, T, H, words) and b (Db, T, H, words), each instance contiguous, instance i at
+ *                         a + i * a_stride words (b likewise, on its own base pointer).
+ *                           inter  (Da, Db) int64  sum over T, H, W of popcount(a & b)
+ *                           area_a (Da, T)  int64, area_b (Db, T) int64
+ *                         Bits beyond `width` in a row's last word are masked by the kernel.  A workgroup
+ *                         takes M2F_PAIR_CHUNK_WORDS word positions of one frame and an M2F_PAIR_TA x
+ *                         M2F_PAIR_TB tile of instances, so a is read ceil(Db / M2F_PAIR_TB) times and b
+ *                         ceil(Da / M2F_PAIR_TA) times; 128-bit loads when both bases are 16-byte aligned and
+ *                         both strides and H * words are multiples of 4, 32-bit loads otherwise.  Per-workgroup
+ *                         int32 partials go to `workspace` (m2f_bits_pair_workspace bytes, contents on entry
+ *                         irrelevant) and are summed in index order: no atomics, no zeroed buffer.
+ *   m2f_bits_pair_tiles   the three constants, for callers that size their batches by them.
+ * Null pointers, non-positive sizes, H * W >= 2^31, a stride smaller than an instance, a misaligned pointer
+ * or a short workspace give M2F_EINVAL; more than 65535 masks, frames or instance tiles M2F_EUNSUPPORTED;
+ * all before any HIP call.
+ * ------------------------------------------------------------------------------------------- */
+enum { M2F_PAIR_TA = 8, M2F_PAIR_TB = 4, M2F_PAIR_CHUNK_WORDS = 4096 };
+int m2f_rle_decode_bits(const int32_t* positions, int64_t total, const int64_t* offsets, int num_masks, int height,
+                        int width, int32_t* out, void* stream);
+int m2f_bits_pair_tiles(int* ta, int* tb, int* chunk_words);
+int m2f_bits_pair_workspace(int da, int db, int frames, int height, int width, int64_t* bytes);
+int m2f_bits_pair_counts(const int32_t* a, int da, int64_t a_stride, const int32_t* b, int db, int64_t b_stride,
+                         int frames, int height, int width, int64_t* inter, int64_t* area_a, int64_t* area_b,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
