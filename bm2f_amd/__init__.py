@@ -9,7 +9,10 @@ from .inference import (MaskFormerInference, instance_inference, panoptic_infere
                         semantic_inference)
 from .mask_criterion import HungarianMatcher, SetCriterion, VideoHungarianMatcher, VideoSetCriterion  # noqa: F401
 from .evaluation import instances_to_coco_json, instances_to_coco_json_video  # noqa: F401
-from .mask_iou import mask_iou, mask_pair_counts, rle_to_bits  # noqa: F401
+from .coco_eval import (COCOEvalResult, COCOEvaluator, COCOGroundTruth, COCOParams,  # noqa: F401
+                        evaluate_coco)
+from .mask_iou import (mask_iou, mask_pair_counts, mask_pair_counts_ragged, rle_to_bits,  # noqa: F401
+                       rle_to_bits_ragged)
 from .rle import counts_to_string, rle_area, rle_decode, rle_encode, string_to_counts  # noqa: F401
 from .swin import D2SwinTransformer, SwinTransformer, window_attention  # noqa: F401
 from .video_criterion import (VideoHungarianMatcherProj, VideoHungarianMatcherProjPair,  # noqa: F401

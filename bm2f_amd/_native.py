@@ -117,6 +117,9 @@ _SIGNATURES = {
     "m2f_bits_pair_tiles": [_p, _p, _p],
     "m2f_bits_pair_workspace": [_i, _i, _i, _i, _i, _p],
     "m2f_bits_pair_counts": [_p, _i, _l, _p, _i, _l, _i, _i, _i, _p, _p, _p, _p, _l, _p],
+    "m2f_rle_decode_bits_ragged": [_p, _l, _p, _i, _p, _p, _p, _l, _p, _l, _p],
+    "m2f_bits_pair_ragged_workspace": [_l, _p],
+    "m2f_bits_pair_counts_ragged": [_p, _l, _p, _i, _p, _l, _p, _l, _p, _l, _l, _p, _p, _p, _p, _l, _p],
 }
 
 

@@ -15,6 +15,22 @@
 //                   over the four waves through LDS, and stored as one int32 partial per (tile, frame, chunk).
 //   sum_kernel      one thread per output sums its partials in index order into int64.
 //
+// The ragged forms serve many images of different sizes per launch (the COCO evaluator):
+//
+//   decode_ragged_kernel   decode_kernel with a per-mask (H, W) and output word offset; a host-built table deals one
+//                          (mask, block of 256 columns) to each workgroup, so the grid is the sum over the masks.
+//   pair_ragged_kernel     pair_kernel with one frame per group and planes given by word offsets into one flat
+//                          buffer; a host-built table deals one (group, a-tile, b-tile, chunk) to each workgroup, so
+//                          the grid is the sum over the groups of their own tiles.  A workgroup takes the 128-bit
+//                          path when the buffer and the offsets of all of its planes are 16-byte aligned (the host
+//                          pads planes to 4 words) and the 32-bit path otherwise; words beyond a plane's end, which
+//                          the wide loads of a padded plane touch, are masked like tail bits.
+//   sum_ragged_kernel      one thread per output finds its group by binary search and sums its partials in order.
+//
+// The tables live in device memory where the entry points cannot read them, so the kernels check every index they
+// take from a table against the sizes passed by value: a malformed table gives unspecified counts, never an access
+// outside the buffers.
+//
 // No atomics and no zeroed buffer: every partial that is summed was stored by the launch before it.
 #include "bm2f.h"
 #include "common.h"
@@ -66,7 +82,9 @@ __global__ void __launch_bounds__(256) decode_kernel(const int32_t* __restrict__
 
 template <bool kWide>
 __device__ __forceinline__ void load4(const uint32_t* __restrict__ p, int i0, int n, uint32_t (&v)[kVec]) {
-  if (kWide) {   // i0 and n are multiples of 4 and p + i0 is 16-byte aligned
+  // i0 is a multiple of 4, p + i0 is 16-byte aligned and the four words lie inside the buffer: n is a multiple of 4
+  // (pair_kernel), or the plane is followed by words the caller masks (pair_ragged_kernel)
+  if (kWide) {
     if (i0 < n) {
       const uint4 q = *reinterpret_cast<const uint4*>(p + i0);
       v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
@@ -76,6 +94,34 @@ __device__ __forceinline__ void load4(const uint32_t* __restrict__ p, int i0, in
   } else {
 #pragma unroll
     for (int k = 0; k < kVec; ++k) v[k] = i0 + k < n ? p[i0 + k] : 0u;
+  }
+}
+
+// the counts of a workgroup -> its kVals int32 partials at `row`: over the wave by shuffles, over the four waves
+// through LDS
+__device__ __forceinline__ void reduce_store(const int (&acc)[kTA][kTB], const int (&na)[kTA], const int (&nb)[kTB],
+                                             int32_t* __restrict__ row) {
+  __shared__ int wave_sum[kThreads / 64][kVals];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  auto reduce = [&](int v, int slot) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_down(v, s);
+    if (lane == 0) wave_sum[wave][slot] = v;
+  };
+#pragma unroll
+  for (int i = 0; i < kTA; ++i)
+#pragma unroll
+    for (int j = 0; j < kTB; ++j) reduce(acc[i][j], i * kTB + j);
+#pragma unroll
+  for (int i = 0; i < kTA; ++i) reduce(na[i], kTA * kTB + i);
+#pragma unroll
+  for (int j = 0; j < kTB; ++j) reduce(nb[j], kTA * kTB + kTA + j);
+  __syncthreads();
+  if (threadIdx.x < kVals) {
+    int s = 0;
+#pragma unroll
+    for (int w = 0; w < kThreads / 64; ++w) s += wave_sum[w][threadIdx.x];
+    row[threadIdx.x] = s;
   }
 }
 
@@ -147,29 +193,8 @@ __global__ void __launch_bounds__(kThreads) pair_kernel(const uint32_t* __restri
     }
   }
 
-  __shared__ int wave_sum[kThreads / 64][kVals];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  auto reduce = [&](int v, int slot) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_down(v, s);
-    if (lane == 0) wave_sum[wave][slot] = v;
-  };
-#pragma unroll
-  for (int i = 0; i < kTA; ++i)
-#pragma unroll
-    for (int j = 0; j < kTB; ++j) reduce(acc[i][j], i * kTB + j);
-#pragma unroll
-  for (int i = 0; i < kTA; ++i) reduce(na[i], kTA * kTB + i);
-#pragma unroll
-  for (int j = 0; j < kTB; ++j) reduce(nb[j], kTA * kTB + kTA + j);
-  __syncthreads();
-  if (threadIdx.x < kVals) {
-    int s = 0;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) s += wave_sum[w][threadIdx.x];
-    const int64_t block = (static_cast<int64_t>(blockIdx.z) * gridDim.y + t) * gridDim.x + chunk;
-    partial[block * kVals + threadIdx.x] = s;
-  }
+  const int64_t block = (static_cast<int64_t>(blockIdx.z) * gridDim.y + t) * gridDim.x + chunk;
+  reduce_store(acc, na, nb, partial + block * kVals);
 }
 
 // one thread per output: inter (Da, Db), then area_a (Da, T), then area_b (Db, T)
@@ -205,6 +230,249 @@ __global__ void __launch_bounds__(256) sum_kernel(const int32_t* __restrict__ pa
   const int32_t* p = partial + (static_cast<int64_t>(tile) * T + t0) * chunks * kVals + slot;
   int64_t s = 0;
   for (int64_t i = 0; i < static_cast<int64_t>(t1 - t0) * chunks; ++i) s += p[i * kVals];
+  *dst = s;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// ragged forms
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kGroupFields = M2F_RAGGED_GROUP_FIELDS;   // H, W, na, nb, a_start, b_start, inter_start, tile_start
+constexpr int64_t kIntMax = 0x7fffffff;
+
+// grid (num_blocks): blocks (num_blocks, 2) int32 = (mask, block of 256 columns)
+__global__ void __launch_bounds__(256) decode_ragged_kernel(const int32_t* __restrict__ positions, int64_t total,
+                                                            const int64_t* __restrict__ offsets, int num_masks,
+                                                            const int32_t* __restrict__ sizes,
+                                                            const int64_t* __restrict__ out_offsets,
+                                                            const int32_t* __restrict__ blocks,
+                                                            int32_t* __restrict__ out, int64_t out_words) {
+  const int m = blocks[2 * static_cast<int64_t>(blockIdx.x)];
+  const int xb = blocks[2 * static_cast<int64_t>(blockIdx.x) + 1];
+  if (m < 0 || m >= num_masks || xb < 0) return;   // uniform over the workgroup, like every return below
+  const int H = sizes[2 * m], W = sizes[2 * m + 1];
+  if (H <= 0 || W <= 0 || static_cast<int64_t>(H) * W > kIntMax) return;
+  if (static_cast<int64_t>(xb) * 256 >= W) return;
+  const int words = (W + 31) / 32;
+  const int64_t o0 = out_offsets[m];
+  if (o0 < 0 || o0 + static_cast<int64_t>(H) * words > out_words) return;
+  const int x = xb * 256 + threadIdx.x;
+  const bool live = x < W;
+  const int64_t begin = min(max(offsets[m], static_cast<int64_t>(0)), total);
+  const int64_t end = min(max(offsets[m + 1], begin), total);
+  const int32_t* t = positions + begin;
+  const int64_t n = live ? end - begin : 0;
+  const int p0 = live ? x * H : 0;
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (t[mid] <= p0) lo = mid + 1; else hi = mid;
+  }
+  int64_t cur = lo;
+  int next = cur < n ? t[cur] : 0x7fffffff;
+  int32_t* o = out + o0 + (x >> 5);
+  const bool writer = (threadIdx.x & 31) == 0 && (x >> 5) < words;
+  const int shift = threadIdx.x & 32;
+  for (int y = 0; y < H; ++y) {
+    const int p = p0 + y;
+    while (next <= p) {
+      ++cur;
+      next = cur < n ? t[cur] : 0x7fffffff;
+    }
+    const unsigned long long vote = __ballot(static_cast<int>(cur & 1));
+    if (writer) o[static_cast<int64_t>(y) * words] = static_cast<int32_t>(static_cast<uint32_t>(vote >> shift));
+  }
+}
+
+// the counts of one workgroup: planes at w + oa[i] / w + ob[j] (a negative offset is an absent plane), word
+// positions [chunk0, chunk0 + kChunk) of frame_words
+__device__ __forceinline__ void ragged_counts(const uint32_t* __restrict__ w, bool wide, const int (&oa)[kTA],
+                                              const int (&ob)[kTB], int64_t chunk0, int frame_words, int words,
+                                              uint32_t tail_mask, int (&acc)[kTA][kTB], int (&na)[kTA],
+                                              int (&nb)[kTB]) {
+#pragma unroll 1
+  for (int it = 0; it < kIters; ++it) {
+    const int64_t pos = chunk0 + (it * kThreads + threadIdx.x) * kVec;
+    if (pos < frame_words) {
+      const int i0 = static_cast<int>(pos);
+      uint32_t keep[kVec];
+      int col = i0 % words;
+#pragma unroll
+      for (int k = 0; k < kVec; ++k) {
+        // beyond the plane's end (the padding a wide load reads) nothing is kept
+        keep[k] = i0 + k < frame_words ? (col == words - 1 ? tail_mask : 0xffffffffu) : 0u;
+        col = col + 1 == words ? 0 : col + 1;
+      }
+      uint32_t va[kTA][kVec], vb[kTB][kVec];
+#pragma unroll
+      for (int i = 0; i < kTA; ++i) {
+        if (oa[i] >= 0) {   // uniform over the workgroup
+          if (wide) load4<true>(w + oa[i], i0, frame_words, va[i]); else load4<false>(w + oa[i], i0, frame_words, va[i]);
+        } else {
+#pragma unroll
+          for (int k = 0; k < kVec; ++k) va[i][k] = 0u;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < kTB; ++j) {
+        if (ob[j] >= 0) {
+          if (wide) load4<true>(w + ob[j], i0, frame_words, vb[j]); else load4<false>(w + ob[j], i0, frame_words, vb[j]);
+        } else {
+#pragma unroll
+          for (int k = 0; k < kVec; ++k) vb[j][k] = 0u;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kVec; ++k) {
+#pragma unroll
+        for (int i = 0; i < kTA; ++i) {
+          va[i][k] &= keep[k];
+          na[i] += __popc(va[i][k]);
+        }
+#pragma unroll
+        for (int j = 0; j < kTB; ++j) {
+          vb[j][k] &= keep[k];
+          nb[j] += __popc(vb[j][k]);
+        }
+#pragma unroll
+        for (int i = 0; i < kTA; ++i)
+#pragma unroll
+          for (int j = 0; j < kTB; ++j) acc[i][j] += __popc(va[i][k] & vb[j][k]);
+      }
+    }
+  }
+}
+
+struct RaggedGroup {
+  int64_t H, W, na, nb, a0, b0, inter0, tile0;
+  int words, frame_words, tiles_b, chunks;
+  bool ok;
+};
+
+__device__ __forceinline__ RaggedGroup load_group(const int64_t* __restrict__ groups, int64_t g, int64_t total_a,
+                                                  int64_t total_b) {
+  const int64_t* d = groups + g * kGroupFields;
+  RaggedGroup r;
+  r.H = d[0], r.W = d[1], r.na = d[2], r.nb = d[3], r.a0 = d[4], r.b0 = d[5], r.inter0 = d[6], r.tile0 = d[7];
+  r.ok = r.H > 0 && r.W > 0 && r.H <= kIntMax && r.W <= kIntMax && r.na >= 0 && r.nb >= 0 && r.na <= kIntMax &&
+         r.nb <= kIntMax && r.a0 >= 0 && r.b0 >= 0 && r.a0 <= total_a - r.na && r.b0 <= total_b - r.nb &&
+         r.inter0 >= 0 && r.tile0 >= 0;
+  r.words = r.ok ? static_cast<int>((r.W + 31) / 32) : 1;
+  r.ok = r.ok && r.H * r.words <= kIntMax;
+  r.frame_words = r.ok ? static_cast<int>(r.H * r.words) : 0;
+  r.tiles_b = r.ok ? static_cast<int>(max((r.nb + kTB - 1) / kTB, static_cast<int64_t>(1))) : 1;
+  r.chunks = (r.frame_words + kChunk - 1) / kChunk;
+  return r;
+}
+
+// grid (num_tiles): tiles (num_tiles, 4) int32 = (group, a-tile, b-tile, chunk); partial row = the table row
+__global__ void __launch_bounds__(kThreads) pair_ragged_kernel(const uint32_t* __restrict__ w, int64_t total_words,
+                                                               int base_wide, const int64_t* __restrict__ groups,
+                                                               int num_groups, const int64_t* __restrict__ a_off,
+                                                               int64_t total_a, const int64_t* __restrict__ b_off,
+                                                               int64_t total_b, const int32_t* __restrict__ tiles,
+                                                               int32_t* __restrict__ partial) {
+  const int32_t* tile = tiles + 4 * static_cast<int64_t>(blockIdx.x);
+  const int g = tile[0], ta = tile[1], tb = tile[2], chunk = tile[3];
+  int acc[kTA][kTB], na[kTA], nb[kTB];
+#pragma unroll
+  for (int i = 0; i < kTA; ++i) {
+    na[i] = 0;
+#pragma unroll
+    for (int j = 0; j < kTB; ++j) acc[i][j] = 0;
+  }
+#pragma unroll
+  for (int j = 0; j < kTB; ++j) nb[j] = 0;
+
+  if (g >= 0 && g < num_groups && ta >= 0 && tb >= 0 && chunk >= 0) {   // uniform; a bad row stores zeros
+    const RaggedGroup r = load_group(groups, g, total_a, total_b);
+    if (r.ok) {
+      const int64_t wide_words = (static_cast<int64_t>(r.frame_words) + 3) & ~static_cast<int64_t>(3);
+      const int64_t ia0 = static_cast<int64_t>(ta) * kTA, ib0 = static_cast<int64_t>(tb) * kTB;
+      int oa[kTA], ob[kTB];   // < 2^31: total_words is checked by the entry point
+      bool wide = base_wide != 0;
+      auto plane = [&](const int64_t* __restrict__ table, int64_t index, int64_t count) -> int {
+        if (index >= count) return -1;
+        const int64_t off = table[index];
+        if (off < 0 || off > total_words - r.frame_words) return -1;
+        wide = wide && (off & 3) == 0 && off <= total_words - wide_words;
+        return static_cast<int>(off);
+      };
+#pragma unroll
+      for (int i = 0; i < kTA; ++i) oa[i] = plane(a_off + r.a0, ia0 + i, r.na);
+#pragma unroll
+      for (int j = 0; j < kTB; ++j) ob[j] = plane(b_off + r.b0, ib0 + j, r.nb);
+      const uint32_t tail_mask = r.W % 32 ? (1u << (r.W % 32)) - 1u : 0xffffffffu;
+      const int64_t chunk0 = static_cast<int64_t>(chunk) * kChunk;
+      ragged_counts(w, wide, oa, ob, chunk0, r.frame_words, r.words, tail_mask, acc, na, nb);
+    }
+  }
+
+  reduce_store(acc, na, nb, partial + static_cast<int64_t>(blockIdx.x) * kVals);
+}
+
+// the last group whose start (field `field`) is <= v; the starts are non-decreasing
+__device__ __forceinline__ int64_t find_group(const int64_t* __restrict__ groups, int num_groups, int field,
+                                              int64_t v) {
+  int64_t lo = 0, hi = num_groups;   // the first group with start > v
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (groups[mid * kGroupFields + field] <= v) lo = mid + 1; else hi = mid;
+  }
+  return lo - 1;
+}
+
+// one thread per output: inter (n_inter), then area_a (total_a), then area_b (total_b)
+__global__ void __launch_bounds__(256) sum_ragged_kernel(const int32_t* __restrict__ partial, int64_t num_tiles,
+                                                         const int64_t* __restrict__ groups, int num_groups,
+                                                         int64_t n_inter, int64_t total_a, int64_t total_b,
+                                                         int64_t* __restrict__ inter, int64_t* __restrict__ area_a,
+                                                         int64_t* __restrict__ area_b) {
+  const int64_t o = blockIdx.x * static_cast<int64_t>(256) + threadIdx.x;
+  if (o >= n_inter + total_a + total_b) return;
+  int64_t* dst;
+  int64_t local;
+  int field;
+  if (o < n_inter) {
+    dst = inter + o, local = o, field = 6;
+  } else if (o < n_inter + total_a) {
+    dst = area_a + (o - n_inter), local = o - n_inter, field = 4;
+  } else {
+    dst = area_b + (o - n_inter - total_a), local = o - n_inter - total_a, field = 5;
+  }
+  int64_t s = 0;
+  const int64_t g = find_group(groups, num_groups, field, local);
+  if (g >= 0) {
+    const RaggedGroup r = load_group(groups, g, total_a, total_b);
+    int64_t tile = -1;
+    int slot = 0;
+    if (r.ok) {
+      if (field == 6) {
+        const int64_t e = local - r.inter0;
+        if (e < r.na * r.nb) {
+          const int64_t i = e / r.nb, j = e % r.nb;
+          tile = (i / kTA) * r.tiles_b + j / kTB;
+          slot = static_cast<int>((i % kTA) * kTB + j % kTB);
+        }
+      } else if (field == 4) {
+        const int64_t i = local - r.a0;
+        if (i < r.na) {
+          tile = (i / kTA) * r.tiles_b;            // the first tile of B
+          slot = static_cast<int>(kTA * kTB + i % kTA);
+        }
+      } else {
+        const int64_t j = local - r.b0;
+        if (j < r.nb) {
+          tile = j / kTB;                          // the first tile of A
+          slot = static_cast<int>(kTA * kTB + kTA + j % kTB);
+        }
+      }
+    }
+    if (tile >= 0) {
+      const int64_t row0 = r.tile0 + tile * r.chunks;
+      for (int c = 0; c < r.chunks; ++c)
+        if (row0 + c < num_tiles) s += partial[(row0 + c) * kVals + slot];
+    }
+  }
   *dst = s;
 }
 
@@ -302,5 +570,70 @@ extern "C" int m2f_bits_pair_counts(const int32_t* a, int da, int64_t a_stride, 
   const int64_t outputs = static_cast<int64_t>(da) * db + static_cast<int64_t>(da + db) * frames;
   sum_kernel<<<m2f::ceil_div(outputs, 256), 256, 0, st>>>(partial, da, db, frames, g.chunks, g.tiles_b, inter,
                                                           area_a, area_b);
+  return m2f::check_launch(fn);
+}
+
+extern "C" int m2f_rle_decode_bits_ragged(const int32_t* positions, int64_t total, const int64_t* offsets,
+                                          int num_masks, const int32_t* sizes, const int64_t* out_offsets,
+                                          const int32_t* blocks, int64_t num_blocks, int32_t* out, int64_t out_words,
+                                          void* stream) {
+  const char* fn = "m2f_rle_decode_bits_ragged";
+  if (!offsets || !sizes || !out_offsets || !out || (!positions && total > 0) || (!blocks && num_blocks > 0))
+    return m2f::fail(M2F_EINVAL, "%s: null pointer", fn);
+  if (num_masks <= 0 || total < 0 || num_blocks < 0 || out_words < 0)
+    return m2f::fail(M2F_EINVAL, "%s: sizes must be positive", fn);
+  if (!m2f::aligned(positions, 4) || !m2f::aligned(out, 4) || !m2f::aligned(sizes, 4) || !m2f::aligned(blocks, 4) ||
+      !m2f::aligned(offsets, 8) || !m2f::aligned(out_offsets, 8))
+    return m2f::fail(M2F_EINVAL, "%s: int32 arrays must be 4-byte aligned, int64 arrays 8-byte aligned", fn);
+  if (num_blocks > kIntMax) return m2f::fail(M2F_EUNSUPPORTED, "%s: more than 2^31 - 1 column blocks", fn);
+  if (num_blocks == 0) return m2f::ok();
+  decode_ragged_kernel<<<static_cast<unsigned>(num_blocks), 256, 0, static_cast<hipStream_t>(stream)>>>(
+      positions, total, offsets, num_masks, sizes, out_offsets, blocks, out, out_words);
+  return m2f::check_launch(fn);
+}
+
+extern "C" int m2f_bits_pair_ragged_workspace(int64_t num_tiles, int64_t* bytes) {
+  const char* fn = "m2f_bits_pair_ragged_workspace";
+  if (!bytes) return m2f::fail(M2F_EINVAL, "%s: null pointer", fn);
+  if (num_tiles < 0) return m2f::fail(M2F_EINVAL, "%s: a negative number of tiles", fn);
+  if (num_tiles > kIntMax) return m2f::fail(M2F_EUNSUPPORTED, "%s: more than 2^31 - 1 tiles", fn);
+  *bytes = num_tiles * kVals * 4;
+  return m2f::ok();
+}
+
+extern "C" int m2f_bits_pair_counts_ragged(const int32_t* words, int64_t total_words, const int64_t* groups,
+                                           int num_groups, const int64_t* a_offsets, int64_t total_a,
+                                           const int64_t* b_offsets, int64_t total_b, const int32_t* tiles,
+                                           int64_t num_tiles, int64_t num_inter, int64_t* inter, int64_t* area_a,
+                                           int64_t* area_b, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* fn = "m2f_bits_pair_counts_ragged";
+  if (!groups || (!words && total_words > 0) || (!a_offsets && total_a > 0) || (!b_offsets && total_b > 0) ||
+      (!tiles && num_tiles > 0) || (!workspace && num_tiles > 0) || (!inter && num_inter > 0) ||
+      (!area_a && total_a > 0) || (!area_b && total_b > 0))
+    return m2f::fail(M2F_EINVAL, "%s: null pointer", fn);
+  if (num_groups <= 0 || total_words < 0 || total_a < 0 || total_b < 0 || num_tiles < 0 || num_inter < 0)
+    return m2f::fail(M2F_EINVAL, "%s: sizes must be positive", fn);
+  if (!m2f::aligned(words, 4) || !m2f::aligned(tiles, 4) || !m2f::aligned(workspace, 4) ||
+      !m2f::aligned(groups, 8) || !m2f::aligned(a_offsets, 8) || !m2f::aligned(b_offsets, 8) ||
+      !m2f::aligned(inter, 8) || !m2f::aligned(area_a, 8) || !m2f::aligned(area_b, 8))
+    return m2f::fail(M2F_EINVAL, "%s: int32 arrays must be 4-byte aligned, int64 arrays 8-byte aligned", fn);
+  if (num_tiles > kIntMax) return m2f::fail(M2F_EUNSUPPORTED, "%s: more than 2^31 - 1 tiles", fn);
+  if (total_words > kIntMax) return m2f::fail(M2F_EUNSUPPORTED, "%s: a buffer of more than 2^31 - 1 words", fn);
+  if (workspace_bytes < num_tiles * kVals * 4)
+    return m2f::fail(M2F_EINVAL, "%s: workspace of %lld bytes, %lld needed", fn,
+                     static_cast<long long>(workspace_bytes), static_cast<long long>(num_tiles * kVals * 4));
+  const int64_t outputs = num_inter + total_a + total_b;
+  if (m2f::ceil_div(outputs, 256) > kIntMax) return m2f::fail(M2F_EUNSUPPORTED, "%s: too many outputs", fn);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int32_t* partial = static_cast<int32_t*>(workspace);
+  if (num_tiles > 0) {
+    pair_ragged_kernel<<<static_cast<unsigned>(num_tiles), kThreads, 0, st>>>(
+        reinterpret_cast<const uint32_t*>(words), total_words, m2f::aligned(words, 16) ? 1 : 0, groups, num_groups,
+        a_offsets, total_a, b_offsets, total_b, tiles, partial);
+    if (const int rc = m2f::check_launch(fn)) return rc;
+  }
+  if (outputs == 0) return m2f::ok();
+  sum_ragged_kernel<<<static_cast<unsigned>(m2f::ceil_div(outputs, 256)), 256, 0, st>>>(
+      partial, num_tiles, groups, num_groups, num_inter, total_a, total_b, inter, area_a, area_b);
   return m2f::check_launch(fn);
 }

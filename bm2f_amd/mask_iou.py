@@ -11,6 +11,10 @@ The planes are those of ``pack_mask_bits`` and of the video head's ``packed=True
 :func:`mask_pair_counts`  planes of Da and Db instance sequences -> intersection (Da, Db) and per-frame areas, summed
                           with popcounts by ``m2f_bits_pair_counts``; only those integers reach the host, in one copy.
 :func:`mask_iou`          counts -> IoU in float64.
+:func:`rle_to_bits_ragged`, :func:`mask_pair_counts_ragged`
+                          the same for masks of many images of different sizes in one flat word buffer: one launch
+                          of ``m2f_rle_decode_bits_ragged`` / ``m2f_bits_pair_counts_ragged`` whatever the number of
+                          images, dealt to workgroups by host-built tables (the COCO evaluator's batch step).
 
 On CPU tensors a numpy restatement of the same definitions runs; that is not a fallback: on a HIP tensor a kernel
 error raises ``NativeError``.
@@ -93,6 +97,12 @@ def _run_ends(rles, size=None):
     H, W = int(size[0]), int(size[1])
     if H <= 0 or W <= 0 or H * W >= 2 ** 31:
         raise ValueError(f"{H} x {W} pixels: sizes must be positive and fit a 32-bit count")
+    positions, offsets = _run_ends_sized(rles, np.full(len(rles), H * W, dtype=np.int64))
+    return positions, offsets, H, W
+
+
+def _run_ends_sized(rles, pixels):
+    """-> (positions, offsets) of masks whose counts must add up to ``pixels[m]``."""
     M = len(rles)
     n = np.zeros(M, dtype=np.int64)
     is_str = np.array([r is not None and isinstance(r["counts"], (str, bytes)) for r in rles], dtype=bool)
@@ -117,9 +127,9 @@ def _run_ends(rles, size=None):
         raise ValueError("negative counts")
     ends = _seg_cumsum(counts, n)
     present = is_str | is_list
-    if (n[present] == 0).any() or (ends[offsets[1:][present] - 1] != H * W).any():
+    if (n[present] == 0).any() or (ends[offsets[1:][present] - 1] != pixels[present]).any():
         raise ValueError("counts do not add up to the mask size")
-    return ends.astype(np.int32), offsets, H, W
+    return ends.astype(np.int32), offsets
 
 
 def _pack_rows(bits):
@@ -263,3 +273,284 @@ def mask_iou(inter, area_a, area_b, iscrowd=None) -> np.ndarray:
     out = np.zeros_like(u)
     np.divide(i, u, out=out, where=u > 0)
     return out
+
+
+# -------------------------------------------------------------------------------------------------------------------
+# ragged forms: masks of many images of different sizes in one flat word buffer
+# -------------------------------------------------------------------------------------------------------------------
+_PLANE_ALIGN = 4                        # words: planes start on 16 bytes so that the pair kernel loads 128 bits
+_GROUP_FIELDS = 8                       # M2F_RAGGED_GROUP_FIELDS
+MAX_RAGGED_WORDS = 2 ** 31 - 1          # m2f_bits_pair_counts_ragged keeps plane offsets in 32 bits
+
+
+def _ragged_sizes(rles, sizes):
+    """-> (M, 2) int64 (H, W) per mask from the masks' own ``size`` and, for ``None`` entries, from ``sizes``."""
+    if sizes is not None and len(sizes) != len(rles):
+        raise ValueError(f"{len(sizes)} sizes for {len(rles)} masks")
+    out = np.zeros((len(rles), 2), dtype=np.int64)
+    for m, r in enumerate(rles):
+        given = None if sizes is None or sizes[m] is None else [int(v) for v in sizes[m]]
+        own = None if r is None else [int(v) for v in r["size"]]
+        if own is None and given is None:
+            raise ValueError(f"mask {m} is None and sizes does not give its (H, W)")
+        if own is not None and given is not None and own != given:
+            raise ValueError(f"mask {m} has size {own}, {given} was expected")
+        H, W = own if own is not None else given
+        if H <= 0 or W <= 0 or H * W >= 2 ** 31:
+            raise ValueError(f"{H} x {W} pixels: sizes must be positive and fit a 32-bit count")
+        out[m] = (H, W)
+    return out
+
+
+def _plane_words(sizes):
+    return sizes[:, 0] * ((sizes[:, 1] + 31) // 32)
+
+
+_PARSE_CHUNK = 1 << 20                  # characters (or list entries) parsed at a time
+
+
+def _run_ends_chunked(rles, pixels):
+    """``_run_ends_sized`` over runs of masks of about ``_PARSE_CHUNK`` characters: the vectorised parser keeps a
+    dozen int64 temporaries per character, and parsing a whole batch of dense masks at once was measured 1.3x slower
+    than parsing it image by image."""
+    size = np.array([0 if r is None else len(r["counts"]) for r in rles], dtype=np.int64)
+    cuts = [0]
+    used = 0
+    for m, n in enumerate(size):
+        if used and used + n > _PARSE_CHUNK:
+            cuts.append(m)
+            used = 0
+        used += n
+    cuts.append(len(rles))
+    if len(cuts) == 2:
+        return _run_ends_sized(rles, pixels)
+    parts = [_run_ends_sized(rles[a:b], pixels[a:b]) for a, b in zip(cuts[:-1], cuts[1:])]
+    base = np.concatenate(([0], np.cumsum([p.size for p, _ in parts])))[:-1]
+    offsets = np.concatenate([o[:-1] + s for (_, o), s in zip(parts, base)] + [[base[-1] + parts[-1][1][-1]]])
+    return np.concatenate([p for p, _ in parts]), offsets.astype(np.int64)
+
+
+def _decode_plan(rles, sizes):
+    """Every check of rle_to_bits_ragged -> (hw (M, 2) int64, out_offsets (M,) int64, total words, the tables of
+    ``m2f_rle_decode_bits_ragged`` as int64-aligned host arrays)."""
+    hw = _ragged_sizes(rles, sizes)
+    positions, offsets = _run_ends_chunked(rles, hw[:, 0] * hw[:, 1])
+    padded = (_plane_words(hw) + _PLANE_ALIGN - 1) // _PLANE_ALIGN * _PLANE_ALIGN
+    out_offsets = np.concatenate(([0], np.cumsum(padded)))[:-1].astype(np.int64)
+    total = int(padded.sum())
+    if total > MAX_RAGGED_WORDS:
+        raise ValueError(f"the planes take {total} words, more than the {MAX_RAGGED_WORDS} of one buffer; "
+                         "split the masks over several calls")
+    nblk =(hw[:, 1] + 255) // 256
+    mask_of = np.repeat(np.arange(len(rles), dtype=np.int64), nblk)
+    first = np.concatenate(([0], np.cumsum(nblk)))[:-1]
+    blocks = np.stack((mask_of, np.arange(mask_of.size) - first[mask_of]), axis=1).astype(np.int32)
+    tables = {"offsets": offsets, "out_offsets": out_offsets, "sizes": hw.astype(np.int32), "blocks": blocks,
+              "positions": positions}
+    return hw, out_offsets, total, tables
+
+
+def _upload(tables, device):
+    """One host-to-device copy of several int32 / int64 arrays, each on an 8-byte boundary -> {name: tensor}."""
+    parts, spans, at = [], {}, 0
+    for name, arr in tables.items():
+        flat = np.ascontiguousarray(arr).reshape(-1)
+        raw = flat.view(np.int32)
+        if raw.size % 2:
+            raw = np.concatenate((raw, np.zeros(1, np.int32)))
+        spans[name] = (at, flat.size, flat.dtype)
+        parts.append(raw)
+        at += raw.size
+    buf = torch.from_numpy(np.concatenate(parts) if at else np.zeros(2, np.int32)).to(device)
+    out = {}
+    for name, (start, n, dtype) in spans.items():
+        if dtype == np.int64:
+            out[name] = buf[start:start + 2 * n].view(torch.int64)
+        else:
+            out[name] = buf[start:start + n]
+    out["_buffer"] = buf
+    return out
+
+
+def _ptr(t):
+    return t.data_ptr() if t.numel() else None
+
+
+def _launch_decode(dev_tables, num_masks, words, device):
+    t = dev_tables
+    with torch.cuda.device(device):
+        _native.call("m2f_rle_decode_bits_ragged", _ptr(t["positions"]), t["positions"].numel(),
+                     t["offsets"].data_ptr(), num_masks, t["sizes"].data_ptr(), t["out_offsets"].data_ptr(),
+                     _ptr(t["blocks"]), t["blocks"].numel() // 2, _ptr(words), words.numel(),
+                     torch.cuda.current_stream(device).cuda_stream)
+
+
+def rle_to_bits_ragged(rles, device=None, sizes=None):
+    """RLE dicts of any sizes (``counts`` as in :func:`rle_to_bits`; an entry may be ``None``, a zero plane whose
+    (H, W) ``sizes[m]`` gives) -> ``(words, offsets, sizes)``: ``words`` a flat int32 tensor on ``device``, mask
+    ``m`` occupying ``H_m * ceil(W_m / 32)`` words at ``offsets[m]`` in the layout of ``pack_mask_bits`` with zero
+    tail bits; ``offsets`` (M,) int64 and ``sizes`` (M, 2) int64 host arrays.  Planes start on multiples of 4 words
+    (16 bytes), which lets ``mask_pair_counts_ragged`` load 128 bits at a time; the padding words between planes are
+    unspecified on the device (zero on the CPU) and every consumer here ignores them.  On a HIP device one upload
+    and one launch of ``m2f_rle_decode_bits_ragged`` whatever the number of masks and sizes.
+
+    Raises ValueError, before any launch, on what :func:`rle_to_bits` refuses, when a mask's size contradicts
+    ``sizes`` or a ``None`` entry has none, and when the planes take more than ``MAX_RAGGED_WORDS`` words."""
+    device = torch.device("cpu" if device is None else device)
+    rles = list(rles)
+    if not rles:
+        return torch.zeros(0, dtype=torch.int32, device=device), np.zeros(0, np.int64), np.zeros((0, 2), np.int64)
+    hw, out_offsets, total, tables = _decode_plan(rles, sizes)
+    if device.type != "cuda":
+        words = np.zeros(total, dtype=np.int32)
+        pos, off = tables["positions"], tables["offsets"]
+        for m, (H, W) in enumerate(hw):
+            plane = _decode_host(pos[off[m]:off[m + 1]], np.array([0, off[m + 1] - off[m]]), int(H), int(W))
+            words[out_offsets[m]:out_offsets[m] + plane.size] = plane.reshape(-1)
+        return torch.from_numpy(words).to(device), out_offsets, hw
+    dev = _upload(tables, device)
+    words = torch.empty(total, dtype=torch.int32, device=device)
+    _launch_decode(dev, len(rles), words, device)
+    return words, out_offsets, hw
+
+
+def _pair_plan(groups, total_words):
+    """Every check of mask_pair_counts_ragged -> (per-group (na, nb), the tables of ``m2f_bits_pair_counts_ragged``,
+    number of tile rows)."""
+    TA, TB, CHUNK = pair_tiles()
+    G = len(groups)
+    desc = np.zeros((G, _GROUP_FIELDS), dtype=np.int64)
+    a_all, b_all, tiles = [], [], []
+    a0 = b0 = i0 = t0 = 0
+    for g, grp in enumerate(groups):
+        try:
+            H, W, a_off, b_off = grp
+            H, W = int(H), int(W)
+            a_off = np.asarray(a_off, dtype=np.int64).reshape(-1)
+            b_off = np.asarray(b_off, dtype=np.int64).reshape(-1)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"group {g} must be (H, W, a_offsets, b_offsets)") from e
+        if H <= 0 or W <= 0 or H * W >= 2 ** 31:
+            raise ValueError(f"group {g}: {H} x {W} pixels: sizes must be positive and fit a 32-bit count")
+        fw = H * ((W + 31) // 32)
+        for off in (a_off, b_off):
+            if off.size and (off.min() < 0 or off.max() + fw > total_words):
+                raise ValueError(f"group {g}: a plane of {fw} words does not fit the buffer of {total_words}")
+        na, nb = a_off.size, b_off.size
+        desc[g] = (H, W, na, nb, a0, b0, i0, t0)
+        a_all.append(a_off)
+        b_all.append(b_off)
+        if na or nb:
+            ta, tb, ch = max(1, -(-na // TA)), max(1, -(-nb // TB)), -(-fw // CHUNK)
+            idx = np.arange(ta * tb * ch, dtype=np.int64)
+            tiles.append(np.stack((np.full(idx.size, g), idx // (tb * ch), idx // ch % tb, idx % ch), axis=1))
+            t0 += idx.size
+        a0, b0, i0 = a0 + na, b0 + nb, i0 + na * nb
+    tables = {"groups": desc,
+              "a_off": np.concatenate(a_all) if a_all else np.zeros(0, np.int64),
+              "b_off": np.concatenate(b_all) if b_all else np.zeros(0, np.int64),
+              "tiles": (np.concatenate(tiles) if tiles else np.zeros((0, 4), np.int64)).astype(np.int32)}
+    return desc, tables, t0
+
+
+def _pair_counts_ragged_host(words, desc, tables):
+    out = []
+    for H, W, na, nb, a0, b0, _, _ in desc:
+        wr = (W + 31) // 32
+        fw = H * wr
+
+        def planes(offs):
+            if offs.size == 0:
+                return np.zeros((0, 1, H, wr), dtype=np.int32)
+            return np.stack([words[o:o + fw] for o in offs]).reshape(-1, 1, H, wr)
+        a = planes(tables["a_off"][a0:a0 + na])
+        b = planes(tables["b_off"][b0:b0 + nb])
+        inter, area_a, area_b = _pair_counts_host(a, b, int(W))
+        out.append((inter.reshape(na, nb), area_a.reshape(na), area_b.reshape(nb)))
+    return out
+
+
+def _split_counts(host, desc):
+    """The flat output [inter | area_a | area_b] -> one (inter (na, nb), area_a (na,), area_b (nb,)) per group."""
+    n_inter = int((desc[:, 2] * desc[:, 3]).sum())
+    n_a = int(desc[:, 2].sum())
+    out = []
+    for _, _, na, nb, a0, b0, i0, _ in desc:
+        out.append((host[i0:i0 + na * nb].reshape(na, nb), host[n_inter + a0:n_inter + a0 + na],
+                    host[n_inter + n_a + b0:n_inter + n_a + b0 + nb]))
+    return out
+
+
+def _launch_pairs(words, desc, dev_tables, num_tiles, device):
+    """-> the device int64 output [inter | area_a | area_b]."""
+    n_inter = int((desc[:, 2] * desc[:, 3]).sum())
+    n_a, n_b = int(desc[:, 2].sum()), int(desc[:, 3].sum())
+    nbytes = ctypes.c_int64()
+    _native.call("m2f_bits_pair_ragged_workspace", num_tiles, ctypes.byref(nbytes))
+    work = torch.empty(max(nbytes.value // 4, 1), dtype=torch.int32, device=device)
+    out = torch.empty(max(n_inter + n_a + n_b, 1), dtype=torch.int64, device=device)
+    t = dev_tables
+    with torch.cuda.device(device):
+        _native.call("m2f_bits_pair_counts_ragged", _ptr(words), words.numel(), t["groups"].data_ptr(), desc.shape[0],
+                     _ptr(t["a_off"]), n_a, _ptr(t["b_off"]), n_b, _ptr(t["tiles"]), num_tiles, n_inter,
+                     out.data_ptr(), out.data_ptr() + 8 * n_inter, out.data_ptr() + 8 * (n_inter + n_a),
+                     work.data_ptr(), work.numel() * 4, torch.cuda.current_stream(device).cuda_stream)
+    return out[:n_inter + n_a + n_b]
+
+
+def mask_pair_counts_ragged(words, groups):
+    """words: a flat int32 tensor of bit planes (as :func:`rle_to_bits_ragged` returns; any word offsets are
+    accepted, 16-byte aligned ones are read 128 bits at a time); groups: one ``(H, W, a_offsets, b_offsets)`` per
+    image, the word offsets of its ``na`` detection planes and ``nb`` ground-truth planes of ``H x W`` pixels (either
+    may be empty).  -> one ``(inter (na, nb), area_a (na,), area_b (nb,))`` of host int64 arrays per group; set tail
+    bits are ignored.  On a HIP tensor one upload of the tables, the two launches of ``m2f_bits_pair_counts_ragged``
+    whatever the number of groups, and one device-to-host copy.
+
+    Raises ValueError, before any launch, when a group is malformed, a size is not positive, a plane does not lie
+    inside ``words`` or ``words`` holds more than ``MAX_RAGGED_WORDS`` words."""
+    if not torch.is_tensor(words) or words.dim() != 1 or words.dtype != torch.int32 or not words.is_contiguous():
+        raise ValueError("words must be a flat contiguous int32 tensor")
+    if words.numel() > MAX_RAGGED_WORDS:
+        raise ValueError(f"words holds {words.numel()} words, more than the {MAX_RAGGED_WORDS} of one call")
+    groups = list(groups)
+    if not groups:
+        return []
+    desc, tables, num_tiles = _pair_plan(groups, words.numel())
+    if words.device.type != "cuda":
+        return _pair_counts_ragged_host(words.detach().numpy(), desc, tables)
+    dev = _upload(tables, words.device)
+    out = _launch_pairs(words.detach(), desc, dev, num_tiles, words.device)
+    return _split_counts(out.cpu().numpy(), desc)                     # the one copy
+
+
+def rle_pair_counts_ragged(rles, groups, device=None, sizes=None):
+    """:func:`rle_to_bits_ragged` and :func:`mask_pair_counts_ragged` of one batch with a single upload: ``groups``
+    holds ``(H, W, a_masks, b_masks)`` with *indices into* ``rles`` in place of word offsets.  -> the per-group
+    counts.  On a HIP device: one upload, one decode launch, one pair-count call and one copy (the evaluator's
+    batch step)."""
+    device = torch.device("cpu" if device is None else device)
+    rles = list(rles)
+    groups = list(groups)
+    if not groups:
+        return []
+    if not rles:
+        return [(np.zeros((0, 0), np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64)) for _ in groups]
+    hw, out_offsets, total, dtables = _decode_plan(rles, sizes)
+    by_offset = []
+    for g, (H, W, ia, ib) in enumerate(groups):
+        ia, ib = np.asarray(ia, dtype=np.int64).reshape(-1), np.asarray(ib, dtype=np.int64).reshape(-1)
+        for idx in (ia, ib):
+            if idx.size and (idx.min() < 0 or idx.max() >= len(rles)):
+                raise ValueError(f"group {g} names masks outside the batch")
+            if idx.size and ((hw[idx, 0] != int(H)) | (hw[idx, 1] != int(W))).any():
+                raise ValueError(f"group {g}: a mask's size is not the group's {int(H)} x {int(W)}")
+        by_offset.append((H, W, out_offsets[ia], out_offsets[ib]))
+    desc, ptables, num_tiles = _pair_plan(by_offset, total)
+    if device.type != "cuda":
+        words = rle_to_bits_ragged(rles, device, sizes)[0]
+        return _pair_counts_ragged_host(words.numpy(), desc, ptables)
+    dev = _upload({**dtables, **ptables}, device)
+    words = torch.empty(total, dtype=torch.int32, device=device)
+    _launch_decode(dev, len(rles), words, device)
+    out = _launch_pairs(words, desc, dev, num_tiles, device)
+    return _split_counts(out.cpu().numpy(), desc)                     # the one copy

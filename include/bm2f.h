@@ -741,6 +741,54 @@ int m2f_bits_pair_counts(const int32_t* a, int da, int64_t a_stride, const int32
                          int frames, int height, int width, int64_t* inter, int64_t* area_a, int64_t* area_b,
                          void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The ragged forms: masks of many images of different sizes in one launch (COCO instance AP,
+ * bm2f_amd/coco_eval.py).  All planes live in one flat int32 word buffer; plane m of H_m x W_m pixels
+ * occupies H_m * ceil(W_m / 32) words at a word offset the caller chooses, in the layout above.  The
+ * tables are built by the caller on the host and passed in device memory (one upload carries them all;
+ * mask_iou.rle_to_bits_ragged and mask_pair_counts_ragged are the model callers).  The kernels check every
+ * index they take from a table against the sizes passed here by value: a malformed table gives unspecified
+ * values, never an access outside positions, words, the workspace or the outputs.
+ *
+ *   m2f_rle_decode_bits_ragged   positions / total / offsets as m2f_rle_decode_bits.  sizes (M, 2) int32 =
+ *                         (H, W) per mask; out_offsets (M) int64 = the word offset of mask m in out
+ *                         (out_words words); blocks (num_blocks, 2) int32 = (mask, block of 256 columns),
+ *                         one row per workgroup: ceil(W_m / 256) rows for mask m, so the grid is the sum over
+ *                         the masks and not M times the widest.  Every word of every plane is stored exactly
+ *                         once, tail bits zero; words between planes (padding) are not written.
+ *   m2f_bits_pair_counts_ragged  a batch of groups (a group is one image).  groups (G,
+ *                         M2F_RAGGED_GROUP_FIELDS) int64 = H, W, na, nb, a_start, b_start, inter_start,
+ *                         tile_start: the group's planes are words + a_offsets[a_start + i], i < na, and
+ *                         words + b_offsets[b_start + j], j < nb (a_offsets (total_a), b_offsets (total_b)
+ *                         int64 word offsets); a_start, b_start and inter_start are the running sums of na, nb
+ *                         and na * nb, tile_start of the group's tile rows.  tiles (num_tiles, 4) int32 =
+ *                         (group, a-tile, b-tile, chunk), one row per workgroup, for group g in the order
+ *                         ((a-tile * tiles_b + b-tile) * chunks + chunk) with tiles_a = max(1, ceil(na /
+ *                         M2F_PAIR_TA)), tiles_b = max(1, ceil(nb / M2F_PAIR_TB)), chunks = ceil(H * words /
+ *                         M2F_PAIR_CHUNK_WORDS), and no rows when na = nb = 0: a small image costs its own
+ *                         tiles only.  Outputs, int64:
+ *                           inter  (num_inter = sum na * nb)  group-major, row-major (na, nb) within a group
+ *                           area_a (total_a), area_b (total_b)
+ *                         Two launches whatever G is.  A workgroup uses 128-bit loads when `words` is 16-byte
+ *                         aligned, the offsets of all planes of its tile are multiples of 4 and four-word
+ *                         reads stay inside the buffer, 32-bit loads otherwise; bits beyond W in a row's last
+ *                         word and words beyond the plane's end are masked.  int32 partials per tile row go to
+ *                         `workspace` (m2f_bits_pair_ragged_workspace bytes, contents on entry irrelevant) and
+ *                         are summed in row order: no atomics, no zeroed buffer, the same bytes on every run.
+ * Null pointers, negative sizes, misaligned pointers or a short workspace give M2F_EINVAL; more than 2^31 - 1
+ * table rows M2F_EUNSUPPORTED; all before any HIP call.
+ * ------------------------------------------------------------------------------------------- */
+enum { M2F_RAGGED_GROUP_FIELDS = 8 };
+int m2f_rle_decode_bits_ragged(const int32_t* positions, int64_t total, const int64_t* offsets, int num_masks,
+                               const int32_t* sizes, const int64_t* out_offsets, const int32_t* blocks,
+                               int64_t num_blocks, int32_t* out, int64_t out_words, void* stream);
+int m2f_bits_pair_ragged_workspace(int64_t num_tiles, int64_t* bytes);
+int m2f_bits_pair_counts_ragged(const int32_t* words, int64_t total_words, const int64_t* groups, int num_groups,
+                                const int64_t* a_offsets, int64_t total_a, const int64_t* b_offsets, int64_t total_b,
+                                const int32_t* tiles, int64_t num_tiles, int64_t num_inter, int64_t* inter,
+                                int64_t* area_a, int64_t* area_b, void* workspace, int64_t workspace_bytes,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif
