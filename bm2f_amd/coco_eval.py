@@ -3,8 +3,8 @@ instance_evaluation.py:30-107) gets from ``pycocotools.cocoeval.COCOeval``, rest
 detectron2 on the list ``instances_to_coco_json`` writes.
 
 ``COCOeval`` and the reference's ``YTVOSeval`` (ytvis_api/ytvoseval.py) are one algorithm, the second being a copy of
-the first with ``image`` renamed ``video``; so the matching, accumulation and summary are the functions of
-``bm2f_amd.ytvis_eval``, imported and unchanged, and only what differs for images is written here:
+the first with ``image`` renamed ``video``; the matching, accumulation and summary are those of ``bm2f_amd.ap_eval``,
+shared with the video evaluator, and only what differs for images is written here:
 
   * the IoU of a detection with a crowd ground truth is ``i / area(detection)`` (``maskUtils.iou(d, g, iscrowd)``);
   * a ground truth's area is its annotation's ``area`` field, a detection's is its mask area (``segm``) or
@@ -27,9 +27,9 @@ import json
 
 import numpy as np
 
+from .ap_eval import IMAGE, APEvaluator, EvalResult, evaluate_units, normalize_params
 from .evaluation import instances_to_coco_json
-from .mask_iou import MAX_RAGGED_WORDS, mask_iou, rle_pair_counts_ragged
-from .ytvis_eval import _accumulate, _evaluate_vid, _sorted_dets, _summarize
+from .mask_iou import MAX_RAGGED_WORDS, rle_pair_counts_ragged
 
 DEFAULT_BATCH_BYTES = 64 << 20
 """Bit planes per batch.  A COCO val image with 100 detections and 7 ground truths is ~107 planes of ~38 KB, about
@@ -39,7 +39,7 @@ stores and the pair kernel's loads."""
 
 
 class COCOParams:
-    """``Params.setDetParams`` of cocoeval.py.  ``vidIds`` is ``imgIds`` under the name the shared functions read."""
+    """``Params.setDetParams`` of cocoeval.py."""
 
     def __init__(self, iouType="segm"):
         self.imgIds = []
@@ -51,10 +51,6 @@ class COCOParams:
         self.areaRngLbl = ['all', 'small', 'medium', 'large']
         self.useCats = 1
         self.iouType = iouType
-
-    @property
-    def vidIds(self):
-        return self.imgIds
 
 
 class COCOGroundTruth:
@@ -89,16 +85,8 @@ class COCOGroundTruth:
         return [c["id"] for c in self.dataset.get("categories", [])]
 
 
-class COCOEvalResult:
-    """What ``COCOeval`` holds after ``evaluate()``, ``accumulate()`` and ``summarize()``: ``ious`` {(image,
-    category): (D, G) array or []}, ``evalImgs`` (one record or None per category, area range and image, in that
-    order), ``precision`` (T, R, K, A, M), ``recall`` (T, K, A, M), ``scores`` and the 12 ``stats``."""
-
-    def __init__(self, params, ious, evalImgs, precision, recall, scores, stats):
-        self.params, self.ious, self.evalImgs = params, ious, evalImgs
-        self.precision, self.recall, self.scores, self.stats = precision, recall, scores, stats
-        self.eval = {"params": params, "counts": list(precision.shape), "precision": precision, "recall": recall,
-                     "scores": scores}
+class COCOEvalResult(EvalResult):
+    """What ``COCOeval`` holds after ``evaluate()``, ``accumulate()`` and ``summarize()``."""
 
 
 # -------------------------------------------------------------------------------------------------------------------
@@ -193,80 +181,32 @@ def evaluate_coco(gt, results, iou_type="segm", device=None, params=None,
     ``category_id``, ``score``, ``segmentation`` as RLE, ``bbox`` as xywh).  ``iou_type`` is ``"segm"`` (masks, built
     and counted on ``device`` in batches of ``batch_bytes`` of planes) or ``"bbox"`` (numpy).  Only ``useCats=1``.
 
-    The rules are those of ``evaluate_ytvis`` (ordering, the ``maxDets[-1]`` cut per (image, category), matching
-    thresholds and ties, the crowd re-match, the break on ignore, float32 accumulation, the -1 conventions, the 12
-    statistics) with the COCO differences listed in the module docstring.  An empty pair of one side keeps the
-    ``(D, 0)`` / ``(0, G)`` IoU array of the shared code where ``maskUtils.iou`` returns ``[]``; no number depends
-    on it.
+    The rules (ordering, the ``maxDets[-1]`` cut per (image, category), matching thresholds and ties, the crowd
+    re-match, the break on ignore, float32 accumulation, the -1 conventions, the 12 statistics) are listed in
+    ``bm2f_amd.ap_eval``, with the COCO differences of the module docstring.
 
     Raises ValueError, before any launch, when a result names an unknown image, its mask size is not the image's, or
     (``bbox``) it has no ``bbox``."""
     if iou_type not in ("segm", "bbox"):
         raise NotImplementedError("iou_type must be 'segm' or 'bbox'")
-    p = copy.deepcopy(params) if params is not None else COCOParams(iou_type)
+    p = normalize_params(IMAGE, params if params is not None else COCOParams(iou_type), gt.image_ids(),
+                         gt.category_ids(), results, "results name images the ground truth does not hold")
     p.iouType = iou_type
-    if not p.useCats:
-        raise NotImplementedError("only useCats=1 is supported")
-    img_ids = p.imgIds if len(p.imgIds) else sorted(gt.image_ids())
-    cat_ids = p.catIds if len(p.catIds) else sorted(gt.category_ids())
-    p.imgIds = list(np.unique(img_ids))
-    p.catIds = list(np.unique(cat_ids))
-    p.maxDets = sorted(p.maxDets)
-    maxDet = p.maxDets[-1]
-    known = set(gt.image_ids())
-    if any(r["image_id"] not in known for r in results):
-        raise ValueError("results name images the ground truth does not hold")
-    cats = set(p.catIds)
-
     dets_of = {}
-    for index, r in enumerate(results):
-        dets_of.setdefault(r["image_id"], []).append((index, r))
-    plain = {k: [r for _, r in v] for k, v in dets_of.items()}
+    for r in results:
+        dets_of.setdefault(r["image_id"], []).append(r)
     if iou_type == "segm":
-        counts = _segm_counts(gt, p.imgIds, plain, device, batch_bytes)
+        counts = _segm_counts(gt, p.imgIds, dets_of, device, batch_bytes)
     else:
-        counts = _bbox_counts(gt, p.imgIds, plain)
-
-    gts_by, dts_by, ious = {}, {}, {}
-    for imgId in p.imgIds:
-        anns, dets = gt.img_to_anns.get(imgId, []), dets_of.get(imgId, [])
-        inter, area_d, area_g = counts.get(imgId, (None, None, None))
-        for j, ann in enumerate(anns):
-            if ann["category_id"] in cats:
-                gts_by.setdefault((imgId, ann["category_id"]), []).append(
-                    {"id": ann["id"], "row": j, "iscrowd": ann.get("iscrowd", 0),
-                     "ignore": bool(ann.get("iscrowd", 0)), "avg_area": ann["area"]})
-        for i, (index, r) in enumerate(dets):
-            if r["category_id"] in cats:
-                dts_by.setdefault((imgId, r["category_id"]), []).append(
-                    {"id": index + 1, "row": i, "score": r["score"], "avg_area": area_d[i]})
-        for catId in p.catIds:
-            g, d = gts_by.get((imgId, catId), []), dts_by.get((imgId, catId), [])
-            if len(g) == 0 and len(d) == 0:
-                ious[imgId, catId] = []
-                continue
-            d = _sorted_dets(d, maxDet)
-            rows_d, rows_g = [x["row"] for x in d], [x["row"] for x in g]
-            if not rows_d or not rows_g:
-                ious[imgId, catId] = np.zeros([len(d), len(g)])
-                continue
-            ious[imgId, catId] = mask_iou(inter[np.ix_(rows_d, rows_g)], area_d[rows_d], area_g[rows_g],
-                                          iscrowd=[x["iscrowd"] for x in g])
-
-    evalImgs = [_evaluate_vid(p, gts_by.get((imgId, catId), []), dts_by.get((imgId, catId), []), ious[imgId, catId],
-                              imgId, catId, aRng, maxDet)
-                for catId in p.catIds for aRng in p.areaRng for imgId in p.imgIds]
-    for e in evalImgs:
-        if e is not None:
-            e["image_id"] = e.pop("video_id")
-    precision, recall, scores = _accumulate(p, evalImgs)
-    return COCOEvalResult(p, ious, evalImgs, precision, recall, scores, _summarize(p, precision, recall))
+        counts = _bbox_counts(gt, p.imgIds, dets_of)
+    return evaluate_units(p, IMAGE, gt.img_to_anns, results, lambda imgId, anns, dets: counts[imgId],
+                          lambda ann: ann["area"], lambda r, area: area, crowd_iou=True, result_cls=COCOEvalResult)
 
 
 # -------------------------------------------------------------------------------------------------------------------
 # the evaluator
 # -------------------------------------------------------------------------------------------------------------------
-class COCOEvaluator:
+class COCOEvaluator(APEvaluator):
     """The reference's ``InstanceSegEvaluator`` without detectron2: ``reset()``, ``process(inputs, outputs)`` per
     batch of images and ``evaluate()``.
 
@@ -275,26 +215,16 @@ class COCOEvaluator:
     ``results`` is the accumulated ``coco_instances_results.json`` list with the head's contiguous category ids;
     ``evaluate`` maps them back through ``thing_dataset_id_to_contiguous_id`` (instance_evaluation.py:52-70)."""
 
-    METRICS = ["AP", "AP50", "AP75", "APs", "APm", "APl", "AR1", "AR10"]
-
     def __init__(self, ground_truth, thing_dataset_id_to_contiguous_id=None, class_names=None, device=None,
                  params=None, tasks=("segm",), batch_bytes=DEFAULT_BATCH_BYTES):
-        self.gt = ground_truth if isinstance(ground_truth, COCOGroundTruth) else COCOGroundTruth(ground_truth)
-        self.id_map = thing_dataset_id_to_contiguous_id
-        self.class_names = class_names
-        self.device = device
-        self.params = params
         self.tasks = tuple(tasks)
         self.batch_bytes = batch_bytes
-        self.reset()
+        gt = ground_truth if isinstance(ground_truth, COCOGroundTruth) else COCOGroundTruth(ground_truth)
+        super().__init__(gt, thing_dataset_id_to_contiguous_id, class_names, device, params)
 
     def reset(self):
-        self._predictions = []
+        super().reset()
         self.last = {}
-
-    @property
-    def results(self):
-        return self._predictions
 
     def process(self, inputs, outputs):
         for inp, out in zip(inputs, outputs):
@@ -324,19 +254,9 @@ class COCOEvaluator:
             assert task in {"bbox", "segm"}, f"Got unknown task: {task}!"
             if len(predictions) == 0:
                 self.last[task] = None
-                out[task] = {m: float("nan") for m in self.METRICS}
-                continue
-            params = copy.deepcopy(self.params) if self.params is not None else None
-            r = evaluate_coco(self.gt, predictions, iou_type=task, device=self.device, params=params,
-                              batch_bytes=self.batch_bytes)
-            self.last[task] = r
-            res = {m: float(r.stats[i] * 100 if r.stats[i] >= 0 else "nan") for i, m in enumerate(self.METRICS)}
-            names = self.class_names
-            if names is not None and len(names) > 1:
-                assert len(names) == r.precision.shape[2]
-                for idx, name in enumerate(names):
-                    pr = r.precision[:, :, idx, 0, -1]
-                    pr = pr[pr > -1]
-                    res["AP-" + "{}".format(name)] = float(np.mean(pr) * 100) if pr.size else float("nan")
-            out[task] = res
+            else:
+                params = copy.deepcopy(self.params) if self.params is not None else None
+                self.last[task] = evaluate_coco(self.gt, predictions, iou_type=task, device=self.device,
+                                                params=params, batch_bytes=self.batch_bytes)
+            out[task] = self._derive(self.last[task])
         return out

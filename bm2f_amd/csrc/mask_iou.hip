@@ -1,35 +1,34 @@
 // Mask IoU of instance sequences on one-bit-per-pixel planes (the format is restated in include/bm2f.h).
 //
-//   decode_kernel   the reverse of rle.hip: run ends (cumulative counts in the column-major order p = x * H + y)
-//                   -> bit planes (M, H, words).  A lane owns one column of one mask and the lanes of a wave own 64
+// The uniform kernels serve the instance sequences of one video, all of one size; the ragged kernels serve many
+// images of different sizes per launch (the COCO evaluator), dealt to workgroups by host-built tables.  Both are the
+// same three device pieces and differ only in where a workgroup's arguments come from:
+//
+//   decode_column   the reverse of rle.hip: run ends (cumulative counts in the column-major order p = x * H + y) ->
+//                   a bit plane (H, words).  A lane owns one column of one mask and the lanes of a wave own 64
 //                   consecutive columns.  The pixel p is set when an odd number of run ends is <= p, so the lane
 //                   finds the number of ends <= x * H by a binary search and walks its H rows with a cursor; a wave
 //                   ballot per row is the two words of those 64 columns, stored by lanes 0 and 32.  Lanes beyond W
-//                   vote 0, which zeroes the tail bits.  Every word of the output is stored exactly once.
+//                   vote 0, which zeroes the tail bits.  Every word of the plane is stored exactly once.
+//   tile_counts     inter[d][g] = sum popcount(a_d & b_g), area_a[d], area_b[g] of a kTA x kTB tile of planes over
+//                   kChunk word positions of one frame.  A thread loads 4 consecutive words (one 128-bit load where
+//                   every plane is 16-byte aligned) of each of the kTA + kTB planes and keeps the kVals counts in
+//                   registers; tail bits of a row's last word are masked here.  reduce_store sums the counts over
+//                   the wave by shuffles, over the four waves through LDS, and stores one int32 partial per workgroup.
+//   sum_slot        the tile whose partials hold an output of inter, area_a or area_b, and its slot among them; one
+//                   thread per output sums its partials in index order into int64.
 //
-//   pair_kernel     inter[d][g] = sum popcount(a_d & b_g), area_a[d][t], area_b[g][t].  A workgroup takes kChunk
-//                   word positions of one frame and a kTA x kTB tile of instances; a thread loads 4 consecutive words
-//                   (one 128-bit load) of each of the kTA + kTB instances and keeps the kTA * kTB + kTA + kTB counts
-//                   in registers.  A is read ceil(Db / kTB) times and B ceil(Da / kTA) times per launch.  The tail
-//                   bits of a row's last word are masked here.  The counts are reduced over the wave by shuffles,
-//                   over the four waves through LDS, and stored as one int32 partial per (tile, frame, chunk).
-//   sum_kernel      one thread per output sums its partials in index order into int64.
+//   decode_kernel, pair_kernel, sum_kernel   grids (ceil(W / 256), M), (chunks, T, tiles) and one thread per output:
+//       the block indices are the arguments.  A is read ceil(Db / kTB) times and B ceil(Da / kTA) times per launch.
+//   decode_ragged_kernel   a per-mask (H, W) and output word offset; a table row is (mask, block of 256 columns).
+//   pair_ragged_kernel     one frame per group, planes at word offsets into one flat buffer; a table row is (group,
+//       a-tile, b-tile, chunk).  A workgroup loads 128 bits when the buffer and all of its planes' offsets are 16-byte
+//       aligned (the host pads planes to 4 words); the words such a load reads beyond a plane's end are dropped.
+//   sum_ragged_kernel      finds its group by binary search.
 //
-// The ragged forms serve many images of different sizes per launch (the COCO evaluator):
-//
-//   decode_ragged_kernel   decode_kernel with a per-mask (H, W) and output word offset; a host-built table deals one
-//                          (mask, block of 256 columns) to each workgroup, so the grid is the sum over the masks.
-//   pair_ragged_kernel     pair_kernel with one frame per group and planes given by word offsets into one flat
-//                          buffer; a host-built table deals one (group, a-tile, b-tile, chunk) to each workgroup, so
-//                          the grid is the sum over the groups of their own tiles.  A workgroup takes the 128-bit
-//                          path when the buffer and the offsets of all of its planes are 16-byte aligned (the host
-//                          pads planes to 4 words) and the 32-bit path otherwise; words beyond a plane's end, which
-//                          the wide loads of a padded plane touch, are masked like tail bits.
-//   sum_ragged_kernel      one thread per output finds its group by binary search and sums its partials in order.
-//
-// The tables live in device memory where the entry points cannot read them, so the kernels check every index they
-// take from a table against the sizes passed by value: a malformed table gives unspecified counts, never an access
-// outside the buffers.
+// The tables live in device memory where the entry points cannot read them, so the ragged kernels check every index
+// they take from a table against the sizes passed by value: a malformed table gives unspecified counts, never an
+// access outside the buffers.
 //
 // No atomics and no zeroed buffer: every partial that is summed was stored by the launch before it.
 #include "bm2f.h"
@@ -45,19 +44,21 @@ constexpr int kChunk = kThreads * kVec * kIters;          // word positions of o
 constexpr int kVals = kTA * kTB + kTA + kTB;
 static_assert(kChunk == M2F_PAIR_CHUNK_WORDS, "header constant");
 static_assert(kVals <= kThreads, "one thread per value in the cross-wave sum");
+constexpr int kGroupFields = M2F_RAGGED_GROUP_FIELDS;   // H, W, na, nb, a_start, b_start, inter_start, tile_start
+constexpr int64_t kIntMax = 0x7fffffff;
 
-// grid (ceil(W / 256), M)
-__global__ void __launch_bounds__(256) decode_kernel(const int32_t* __restrict__ positions, int64_t total,
-                                                     const int64_t* __restrict__ offsets, int H, int W, int words,
-                                                     int32_t* __restrict__ out) {
-  const int m = blockIdx.y;
-  const int x = blockIdx.x * 256 + threadIdx.x;
+// Column x of mask m -> bit x % 32 of word x / 32 of the H rows of `plane`.  Thread i of a workgroup of 256 has
+// x = 256 * k + i, and every thread of a wave calls this, lanes beyond W included: the rows are wave ballots.
+// H * W < 2^31: checked by the callers.
+__device__ __forceinline__ void decode_column(const int32_t* __restrict__ positions, int64_t total,
+                                              const int64_t* __restrict__ offsets, int m, int x, int H, int W,
+                                              int words, int32_t* __restrict__ plane) {
   const bool live = x < W;
   const int64_t begin = min(max(offsets[m], static_cast<int64_t>(0)), total);
   const int64_t end = min(max(offsets[m + 1], begin), total);
-  const int32_t* t = positions + begin;
+  const int32_t* t = positions + begin;   // the run ends of the mask, clamped to the buffer
   const int64_t n = live ? end - begin : 0;
-  const int p0 = live ? x * H : 0;   // < 2^31: checked by the entry point
+  const int p0 = live ? x * H : 0;
   // the number of run ends <= p0
   int64_t lo = 0, hi = n;
   while (lo < hi) {
@@ -66,7 +67,7 @@ __global__ void __launch_bounds__(256) decode_kernel(const int32_t* __restrict__
   }
   int64_t cur = lo;
   int next = cur < n ? t[cur] : 0x7fffffff;
-  int32_t* o = out + static_cast<int64_t>(m) * H * words + (x >> 5);
+  int32_t* o = plane + (x >> 5);
   const bool writer = (threadIdx.x & 31) == 0 && (x >> 5) < words;
   const int shift = threadIdx.x & 32;
   for (int y = 0; y < H; ++y) {
@@ -80,20 +81,65 @@ __global__ void __launch_bounds__(256) decode_kernel(const int32_t* __restrict__
   }
 }
 
-template <bool kWide>
-__device__ __forceinline__ void load4(const uint32_t* __restrict__ p, int i0, int n, uint32_t (&v)[kVec]) {
-  // i0 is a multiple of 4, p + i0 is 16-byte aligned and the four words lie inside the buffer: n is a multiple of 4
-  // (pair_kernel), or the plane is followed by words the caller masks (pair_ragged_kernel)
-  if (kWide) {
-    if (i0 < n) {
-      const uint4 q = *reinterpret_cast<const uint4*>(p + i0);
-      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-      v[0] = v[1] = v[2] = v[3] = 0u;
-    }
+// i0 is a multiple of 4; on the wide path p + i0 is 16-byte aligned and the four words lie inside the buffer: n is a
+// multiple of 4 (pair_kernel), or the plane is followed by words the caller masks (pair_ragged_kernel)
+__device__ __forceinline__ void load4(bool wide, const uint32_t* __restrict__ p, int i0, int n, uint32_t (&v)[kVec]) {
+  if (p == nullptr || (wide && i0 >= n)) {
+    v[0] = v[1] = v[2] = v[3] = 0u;
+  } else if (wide) {
+    const uint4 q = *reinterpret_cast<const uint4*>(p + i0);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
   } else {
 #pragma unroll
     for (int k = 0; k < kVec; ++k) v[k] = i0 + k < n ? p[i0 + k] : 0u;
+  }
+}
+
+// The counts of one workgroup: planes pa[i] / pb[j] of frame_words words in rows of `words` (a null pointer is an
+// absent plane; the pointers and `wide` are uniform over the workgroup), word positions [chunk0, chunk0 + kChunk).
+// With kPadded the words a wide load reads beyond the plane's end are dropped; without it frame_words is a multiple
+// of 4 on the wide path and there are none.
+template <bool kPadded>
+__device__ __forceinline__ void tile_counts(bool wide, const uint32_t* const (&pa)[kTA],
+                                            const uint32_t* const (&pb)[kTB], int64_t chunk0, int frame_words,
+                                            int words, uint32_t tail_mask, int (&acc)[kTA][kTB], int (&na)[kTA],
+                                            int (&nb)[kTB]) {
+#pragma unroll 1
+  for (int it = 0; it < kIters; ++it) {
+    const int64_t pos = chunk0 + (it * kThreads + threadIdx.x) * kVec;   // word position inside the frame
+    if (pos < frame_words) {
+      const int i0 = static_cast<int>(pos);
+      uint32_t keep[kVec];
+      int col = i0 % words;
+#pragma unroll
+      for (int k = 0; k < kVec; ++k) {
+        keep[k] = col == words - 1 ? tail_mask : 0xffffffffu;
+        if (kPadded && i0 + k >= frame_words) keep[k] = 0u;
+        col = col + 1 == words ? 0 : col + 1;
+      }
+      uint32_t va[kTA][kVec], vb[kTB][kVec];
+#pragma unroll
+      for (int i = 0; i < kTA; ++i) load4(wide, pa[i], i0, frame_words, va[i]);
+#pragma unroll
+      for (int j = 0; j < kTB; ++j) load4(wide, pb[j], i0, frame_words, vb[j]);
+#pragma unroll
+      for (int k = 0; k < kVec; ++k) {
+#pragma unroll
+        for (int i = 0; i < kTA; ++i) {
+          va[i][k] &= keep[k];
+          na[i] += __popc(va[i][k]);
+        }
+#pragma unroll
+        for (int j = 0; j < kTB; ++j) {
+          vb[j][k] &= keep[k];
+          nb[j] += __popc(vb[j][k]);
+        }
+#pragma unroll
+        for (int i = 0; i < kTA; ++i)
+#pragma unroll
+          for (int j = 0; j < kTB; ++j) acc[i][j] += __popc(va[i][k] & vb[j][k]);
+      }
+    }
   }
 }
 
@@ -125,6 +171,32 @@ __device__ __forceinline__ void reduce_store(const int (&acc)[kTA][kTB], const i
   }
 }
 
+// Output `local` of inter (nb columns, row-major), area_a or area_b -> the tile (a-tile * tiles_b + b-tile) whose
+// partials hold it and its slot among their kVals values.  The areas are read from the first tile of the other side.
+enum SumPart { kInter, kAreaA, kAreaB };
+__device__ __forceinline__ void sum_slot(SumPart part, int64_t local, int64_t nb, int64_t tiles_b, int64_t* tile,
+                                         int* slot) {
+  if (part == kInter) {
+    const int64_t i = local / nb, j = local % nb;
+    *tile = (i / kTA) * tiles_b + j / kTB;
+    *slot = static_cast<int>((i % kTA) * kTB + j % kTB);
+  } else if (part == kAreaA) {
+    *tile = (local / kTA) * tiles_b;
+    *slot = static_cast<int>(kTA * kTB + local % kTA);
+  } else {
+    *tile = local / kTB;
+    *slot = static_cast<int>(kTA * kTB + kTA + local % kTB);
+  }
+}
+
+// grid (ceil(W / 256), M)
+__global__ void __launch_bounds__(256) decode_kernel(const int32_t* __restrict__ positions, int64_t total,
+                                                     const int64_t* __restrict__ offsets, int H, int W, int words,
+                                                     int32_t* __restrict__ out) {
+  decode_column(positions, total, offsets, blockIdx.y, blockIdx.x * 256 + threadIdx.x, H, W, words,
+                out + static_cast<int64_t>(blockIdx.y) * H * words);
+}
+
 // grid (chunks, T, tiles_a * tiles_b)
 template <bool kWide>
 __global__ void __launch_bounds__(kThreads) pair_kernel(const uint32_t* __restrict__ a, int Da, int64_t stride_a,
@@ -134,7 +206,12 @@ __global__ void __launch_bounds__(kThreads) pair_kernel(const uint32_t* __restri
   const int chunk = blockIdx.x, t = blockIdx.y;
   const int ia0 = (blockIdx.z / tiles_b) * kTA, ib0 = (blockIdx.z % tiles_b) * kTB;
   const int64_t frame = static_cast<int64_t>(t) * frame_words;
-  int acc[kTA][kTB], na[kTA], nb[kTB];
+  const uint32_t *pa[kTA], *pb[kTB];
+#pragma unroll
+  for (int i = 0; i < kTA; ++i) pa[i] = ia0 + i < Da ? a + (ia0 + i) * stride_a + frame : nullptr;
+#pragma unroll
+  for (int j = 0; j < kTB; ++j) pb[j] = ib0 + j < Db ? b + (ib0 + j) * stride_b + frame : nullptr;
+  int acc[kTA][kTB], na[kTA], nb[kTB];   // zeroed in the kernel's body: a helper costs a wave of occupancy
 #pragma unroll
   for (int i = 0; i < kTA; ++i) {
     na[i] = 0;
@@ -143,56 +220,7 @@ __global__ void __launch_bounds__(kThreads) pair_kernel(const uint32_t* __restri
   }
 #pragma unroll
   for (int j = 0; j < kTB; ++j) nb[j] = 0;
-
-  for (int it = 0; it < kIters; ++it) {
-    const int i0 = chunk * kChunk + (it * kThreads + threadIdx.x) * kVec;   // word position inside the frame
-    if (i0 < frame_words) {
-      uint32_t keep[kVec];
-      int col = i0 % words;
-#pragma unroll
-      for (int k = 0; k < kVec; ++k) {
-        keep[k] = col == words - 1 ? tail_mask : 0xffffffffu;
-        col = col + 1 == words ? 0 : col + 1;
-      }
-      uint32_t va[kTA][kVec], vb[kTB][kVec];
-#pragma unroll
-      for (int i = 0; i < kTA; ++i) {
-        if (ia0 + i < Da) {   // uniform over the workgroup
-          load4<kWide>(a + (ia0 + i) * stride_a + frame, i0, frame_words, va[i]);
-        } else {
-#pragma unroll
-          for (int k = 0; k < kVec; ++k) va[i][k] = 0u;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < kTB; ++j) {
-        if (ib0 + j < Db) {
-          load4<kWide>(b + (ib0 + j) * stride_b + frame, i0, frame_words, vb[j]);
-        } else {
-#pragma unroll
-          for (int k = 0; k < kVec; ++k) vb[j][k] = 0u;
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < kVec; ++k) {
-#pragma unroll
-        for (int i = 0; i < kTA; ++i) {
-          va[i][k] &= keep[k];
-          na[i] += __popc(va[i][k]);
-        }
-#pragma unroll
-        for (int j = 0; j < kTB; ++j) {
-          vb[j][k] &= keep[k];
-          nb[j] += __popc(vb[j][k]);
-        }
-#pragma unroll
-        for (int i = 0; i < kTA; ++i)
-#pragma unroll
-          for (int j = 0; j < kTB; ++j) acc[i][j] += __popc(va[i][k] & vb[j][k]);
-      }
-    }
-  }
-
+  tile_counts<false>(kWide, pa, pb, static_cast<int64_t>(chunk) * kChunk, frame_words, words, tail_mask, acc, na, nb);
   const int64_t block = (static_cast<int64_t>(blockIdx.z) * gridDim.y + t) * gridDim.x + chunk;
   reduce_store(acc, na, nb, partial + block * kVals);
 }
@@ -204,40 +232,23 @@ __global__ void __launch_bounds__(256) sum_kernel(const int32_t* __restrict__ pa
   const int64_t g = blockIdx.x * static_cast<int64_t>(256) + threadIdx.x;
   const int64_t n_inter = static_cast<int64_t>(Da) * Db, n_a = static_cast<int64_t>(Da) * T;
   if (g >= n_inter + n_a + static_cast<int64_t>(Db) * T) return;
-  int tile, slot, t0, t1;
-  int64_t* dst;
+  int64_t tile;
+  int slot, t0 = 0, t1 = T;   // inter sums every frame, an area one
+  int64_t* dst = inter + g;
   if (g < n_inter) {
-    const int d = static_cast<int>(g / Db), j = static_cast<int>(g % Db);
-    tile = (d / kTA) * tiles_b + j / kTB;
-    slot = (d % kTA) * kTB + j % kTB;
-    t0 = 0, t1 = T;
-    dst = inter + g;
-  } else if (g < n_inter + n_a) {
-    const int64_t r = g - n_inter;
-    const int d = static_cast<int>(r / T);
-    tile = (d / kTA) * tiles_b;            // the first tile of B
-    slot = kTA * kTB + d % kTA;
-    t0 = static_cast<int>(r % T), t1 = t0 + 1;
-    dst = area_a + r;
+    sum_slot(kInter, g, Db, tiles_b, &tile, &slot);
   } else {
-    const int64_t r = g - n_inter - n_a;
-    const int j = static_cast<int>(r / T);
-    tile = j / kTB;                        // the first tile of A
-    slot = kTA * kTB + kTA + j % kTB;
+    const bool is_a = g < n_inter + n_a;
+    const int64_t r = g - n_inter - (is_a ? 0 : n_a);
+    sum_slot(is_a ? kAreaA : kAreaB, r / T, Db, tiles_b, &tile, &slot);
     t0 = static_cast<int>(r % T), t1 = t0 + 1;
-    dst = area_b + r;
+    dst = (is_a ? area_a : area_b) + r;
   }
-  const int32_t* p = partial + (static_cast<int64_t>(tile) * T + t0) * chunks * kVals + slot;
+  const int32_t* p = partial + (tile * T + t0) * chunks * kVals + slot;
   int64_t s = 0;
   for (int64_t i = 0; i < static_cast<int64_t>(t1 - t0) * chunks; ++i) s += p[i * kVals];
   *dst = s;
 }
-
-// ---------------------------------------------------------------------------------------------------------------
-// ragged forms
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int kGroupFields = M2F_RAGGED_GROUP_FIELDS;   // H, W, na, nb, a_start, b_start, inter_start, tile_start
-constexpr int64_t kIntMax = 0x7fffffff;
 
 // grid (num_blocks): blocks (num_blocks, 2) int32 = (mask, block of 256 columns)
 __global__ void __launch_bounds__(256) decode_ragged_kernel(const int32_t* __restrict__ positions, int64_t total,
@@ -255,91 +266,7 @@ __global__ void __launch_bounds__(256) decode_ragged_kernel(const int32_t* __res
   const int words = (W + 31) / 32;
   const int64_t o0 = out_offsets[m];
   if (o0 < 0 || o0 + static_cast<int64_t>(H) * words > out_words) return;
-  const int x = xb * 256 + threadIdx.x;
-  const bool live = x < W;
-  const int64_t begin = min(max(offsets[m], static_cast<int64_t>(0)), total);
-  const int64_t end = min(max(offsets[m + 1], begin), total);
-  const int32_t* t = positions + begin;
-  const int64_t n = live ? end - begin : 0;
-  const int p0 = live ? x * H : 0;
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (t[mid] <= p0) lo = mid + 1; else hi = mid;
-  }
-  int64_t cur = lo;
-  int next = cur < n ? t[cur] : 0x7fffffff;
-  int32_t* o = out + o0 + (x >> 5);
-  const bool writer = (threadIdx.x & 31) == 0 && (x >> 5) < words;
-  const int shift = threadIdx.x & 32;
-  for (int y = 0; y < H; ++y) {
-    const int p = p0 + y;
-    while (next <= p) {
-      ++cur;
-      next = cur < n ? t[cur] : 0x7fffffff;
-    }
-    const unsigned long long vote = __ballot(static_cast<int>(cur & 1));
-    if (writer) o[static_cast<int64_t>(y) * words] = static_cast<int32_t>(static_cast<uint32_t>(vote >> shift));
-  }
-}
-
-// the counts of one workgroup: planes at w + oa[i] / w + ob[j] (a negative offset is an absent plane), word
-// positions [chunk0, chunk0 + kChunk) of frame_words
-__device__ __forceinline__ void ragged_counts(const uint32_t* __restrict__ w, bool wide, const int (&oa)[kTA],
-                                              const int (&ob)[kTB], int64_t chunk0, int frame_words, int words,
-                                              uint32_t tail_mask, int (&acc)[kTA][kTB], int (&na)[kTA],
-                                              int (&nb)[kTB]) {
-#pragma unroll 1
-  for (int it = 0; it < kIters; ++it) {
-    const int64_t pos = chunk0 + (it * kThreads + threadIdx.x) * kVec;
-    if (pos < frame_words) {
-      const int i0 = static_cast<int>(pos);
-      uint32_t keep[kVec];
-      int col = i0 % words;
-#pragma unroll
-      for (int k = 0; k < kVec; ++k) {
-        // beyond the plane's end (the padding a wide load reads) nothing is kept
-        keep[k] = i0 + k < frame_words ? (col == words - 1 ? tail_mask : 0xffffffffu) : 0u;
-        col = col + 1 == words ? 0 : col + 1;
-      }
-      uint32_t va[kTA][kVec], vb[kTB][kVec];
-#pragma unroll
-      for (int i = 0; i < kTA; ++i) {
-        if (oa[i] >= 0) {   // uniform over the workgroup
-          if (wide) load4<true>(w + oa[i], i0, frame_words, va[i]); else load4<false>(w + oa[i], i0, frame_words, va[i]);
-        } else {
-#pragma unroll
-          for (int k = 0; k < kVec; ++k) va[i][k] = 0u;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < kTB; ++j) {
-        if (ob[j] >= 0) {
-          if (wide) load4<true>(w + ob[j], i0, frame_words, vb[j]); else load4<false>(w + ob[j], i0, frame_words, vb[j]);
-        } else {
-#pragma unroll
-          for (int k = 0; k < kVec; ++k) vb[j][k] = 0u;
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < kVec; ++k) {
-#pragma unroll
-        for (int i = 0; i < kTA; ++i) {
-          va[i][k] &= keep[k];
-          na[i] += __popc(va[i][k]);
-        }
-#pragma unroll
-        for (int j = 0; j < kTB; ++j) {
-          vb[j][k] &= keep[k];
-          nb[j] += __popc(vb[j][k]);
-        }
-#pragma unroll
-        for (int i = 0; i < kTA; ++i)
-#pragma unroll
-          for (int j = 0; j < kTB; ++j) acc[i][j] += __popc(va[i][k] & vb[j][k]);
-      }
-    }
-  }
+  decode_column(positions, total, offsets, m, xb * 256 + threadIdx.x, H, W, words, out + o0);
 }
 
 struct RaggedGroup {
@@ -382,28 +309,27 @@ __global__ void __launch_bounds__(kThreads) pair_ragged_kernel(const uint32_t* _
   }
 #pragma unroll
   for (int j = 0; j < kTB; ++j) nb[j] = 0;
-
   if (g >= 0 && g < num_groups && ta >= 0 && tb >= 0 && chunk >= 0) {   // uniform; a bad row stores zeros
     const RaggedGroup r = load_group(groups, g, total_a, total_b);
     if (r.ok) {
       const int64_t wide_words = (static_cast<int64_t>(r.frame_words) + 3) & ~static_cast<int64_t>(3);
       const int64_t ia0 = static_cast<int64_t>(ta) * kTA, ib0 = static_cast<int64_t>(tb) * kTB;
-      int oa[kTA], ob[kTB];   // < 2^31: total_words is checked by the entry point
+      const uint32_t *pa[kTA], *pb[kTB];
       bool wide = base_wide != 0;
-      auto plane = [&](const int64_t* __restrict__ table, int64_t index, int64_t count) -> int {
-        if (index >= count) return -1;
+      auto plane = [&](const int64_t* __restrict__ table, int64_t index, int64_t count) -> const uint32_t* {
+        if (index >= count) return nullptr;
         const int64_t off = table[index];
-        if (off < 0 || off > total_words - r.frame_words) return -1;
+        if (off < 0 || off > total_words - r.frame_words) return nullptr;
         wide = wide && (off & 3) == 0 && off <= total_words - wide_words;
-        return static_cast<int>(off);
+        return w + off;
       };
 #pragma unroll
-      for (int i = 0; i < kTA; ++i) oa[i] = plane(a_off + r.a0, ia0 + i, r.na);
+      for (int i = 0; i < kTA; ++i) pa[i] = plane(a_off + r.a0, ia0 + i, r.na);
 #pragma unroll
-      for (int j = 0; j < kTB; ++j) ob[j] = plane(b_off + r.b0, ib0 + j, r.nb);
+      for (int j = 0; j < kTB; ++j) pb[j] = plane(b_off + r.b0, ib0 + j, r.nb);
       const uint32_t tail_mask = r.W % 32 ? (1u << (r.W % 32)) - 1u : 0xffffffffu;
-      const int64_t chunk0 = static_cast<int64_t>(chunk) * kChunk;
-      ragged_counts(w, wide, oa, ob, chunk0, r.frame_words, r.words, tail_mask, acc, na, nb);
+      tile_counts<true>(wide, pa, pb, static_cast<int64_t>(chunk) * kChunk, r.frame_words, r.words, tail_mask, acc, na,
+                        nb);
     }
   }
 
@@ -429,51 +355,36 @@ __global__ void __launch_bounds__(256) sum_ragged_kernel(const int32_t* __restri
                                                          int64_t* __restrict__ area_b) {
   const int64_t o = blockIdx.x * static_cast<int64_t>(256) + threadIdx.x;
   if (o >= n_inter + total_a + total_b) return;
-  int64_t* dst;
-  int64_t local;
-  int field;
-  if (o < n_inter) {
-    dst = inter + o, local = o, field = 6;
-  } else if (o < n_inter + total_a) {
-    dst = area_a + (o - n_inter), local = o - n_inter, field = 4;
-  } else {
-    dst = area_b + (o - n_inter - total_a), local = o - n_inter - total_a, field = 5;
-  }
+  const SumPart part = o < n_inter ? kInter : o < n_inter + total_a ? kAreaA : kAreaB;
+  const int64_t local = o - (part == kInter ? 0 : part == kAreaA ? n_inter : n_inter + total_a);
+  int64_t* dst = (part == kInter ? inter : part == kAreaA ? area_a : area_b) + local;
   int64_t s = 0;
-  const int64_t g = find_group(groups, num_groups, field, local);
+  // the group fields inter_start, a_start, b_start
+  const int64_t g = find_group(groups, num_groups, part == kInter ? 6 : part == kAreaA ? 4 : 5, local);
   if (g >= 0) {
     const RaggedGroup r = load_group(groups, g, total_a, total_b);
-    int64_t tile = -1;
-    int slot = 0;
-    if (r.ok) {
-      if (field == 6) {
-        const int64_t e = local - r.inter0;
-        if (e < r.na * r.nb) {
-          const int64_t i = e / r.nb, j = e % r.nb;
-          tile = (i / kTA) * r.tiles_b + j / kTB;
-          slot = static_cast<int>((i % kTA) * kTB + j % kTB);
-        }
-      } else if (field == 4) {
-        const int64_t i = local - r.a0;
-        if (i < r.na) {
-          tile = (i / kTA) * r.tiles_b;            // the first tile of B
-          slot = static_cast<int>(kTA * kTB + i % kTA);
-        }
-      } else {
-        const int64_t j = local - r.b0;
-        if (j < r.nb) {
-          tile = j / kTB;                          // the first tile of A
-          slot = static_cast<int>(kTA * kTB + kTA + j % kTB);
-        }
-      }
-    }
-    if (tile >= 0) {
+    const int64_t e = local - (part == kInter ? r.inter0 : part == kAreaA ? r.a0 : r.b0);
+    if (r.ok && e < (part == kInter ? r.na * r.nb : part == kAreaA ? r.na : r.nb)) {
+      int64_t tile;
+      int slot;
+      sum_slot(part, e, r.nb, r.tiles_b, &tile, &slot);
       const int64_t row0 = r.tile0 + tile * r.chunks;
       for (int c = 0; c < r.chunks; ++c)
         if (row0 + c < num_tiles) s += partial[(row0 + c) * kVals + slot];
     }
   }
   *dst = s;
+}
+
+template <size_t kBytes, class... P>
+bool all_aligned(const P*... p) {
+  return (m2f::aligned(p, kBytes) && ...);
+}
+
+int check_pixels(const char* fn, int height, int width) {
+  if (static_cast<int64_t>(height) * width > kIntMax)
+    return m2f::fail(M2F_EINVAL, "%s: %d x %d pixels do not fit a 32-bit count", fn, height, width);
+  return M2F_OK;
 }
 
 struct PairGeom {
@@ -484,8 +395,7 @@ struct PairGeom {
 int pair_geom(const char* fn, int da, int db, int frames, int height, int width, PairGeom* g) {
   if (da <= 0 || db <= 0 || frames <= 0 || height <= 0 || width <= 0)
     return m2f::fail(M2F_EINVAL, "%s: sizes must be positive", fn);
-  if (static_cast<int64_t>(height) * width > 0x7fffffff)
-    return m2f::fail(M2F_EINVAL, "%s: %d x %d pixels do not fit a 32-bit count", fn, height, width);
+  if (const int rc = check_pixels(fn, height, width)) return rc;
   g->words = (width + 31) / 32;
   g->frame_words = height * g->words;
   g->chunks = static_cast<int>(m2f::ceil_div(g->frame_words, kChunk));
@@ -505,9 +415,8 @@ extern "C" int m2f_rle_decode_bits(const int32_t* positions, int64_t total, cons
   if (!offsets || !out || (!positions && total > 0)) return m2f::fail(M2F_EINVAL, "%s: null pointer", fn);
   if (num_masks <= 0 || height <= 0 || width <= 0 || total < 0)
     return m2f::fail(M2F_EINVAL, "%s: sizes must be positive", fn);
-  if (static_cast<int64_t>(height) * width > 0x7fffffff)
-    return m2f::fail(M2F_EINVAL, "%s: %d x %d pixels do not fit a 32-bit count", fn, height, width);
-  if (!m2f::aligned(positions, 4) || !m2f::aligned(out, 4) || !m2f::aligned(offsets, 8))
+  if (const int rc = check_pixels(fn, height, width)) return rc;
+  if (!all_aligned<4>(positions, out) || !all_aligned<8>(offsets))
     return m2f::fail(M2F_EINVAL, "%s: positions and out must be 4-byte aligned, offsets 8-byte aligned", fn);
   if (num_masks > 65535) return m2f::fail(M2F_EUNSUPPORTED, "%s: more than 65535 masks in one call", fn);
   const dim3 grid(m2f::ceil_div(width, 256), num_masks);
@@ -545,8 +454,7 @@ extern "C" int m2f_bits_pair_counts(const int32_t* a, int da, int64_t a_stride, 
   if ((da > 1 && a_stride < instance) || (db > 1 && b_stride < instance) || a_stride < 0 || b_stride < 0)
     return m2f::fail(M2F_EINVAL, "%s: instance stride is smaller than the instance (%lld words)", fn,
                      static_cast<long long>(instance));
-  if (!m2f::aligned(a, 4) || !m2f::aligned(b, 4) || !m2f::aligned(workspace, 4) || !m2f::aligned(inter, 8) ||
-      !m2f::aligned(area_a, 8) || !m2f::aligned(area_b, 8))
+  if (!all_aligned<4>(a, b, workspace) || !all_aligned<8>(inter, area_a, area_b))
     return m2f::fail(M2F_EINVAL, "%s: planes and workspace must be 4-byte aligned, outputs 8-byte aligned", fn);
   if (workspace_bytes < g.partial_bytes)
     return m2f::fail(M2F_EINVAL, "%s: workspace of %lld bytes, %lld needed", fn,
@@ -558,14 +466,9 @@ extern "C" int m2f_bits_pair_counts(const int32_t* a, int da, int64_t a_stride, 
   const uint32_t* ub = reinterpret_cast<const uint32_t*>(b);
   int32_t* partial = static_cast<int32_t*>(workspace);
   // 128-bit loads need every instance and frame to start on 16 bytes
-  const bool wide = m2f::aligned(a, 16) && m2f::aligned(b, 16) && a_stride % 4 == 0 && b_stride % 4 == 0 &&
-                    g.frame_words % 4 == 0;
-  if (wide)
-    pair_kernel<true><<<grid, kThreads, 0, st>>>(ua, da, a_stride, ub, db, b_stride, g.frame_words, g.words,
-                                                 tail_mask, g.tiles_b, partial);
-  else
-    pair_kernel<false><<<grid, kThreads, 0, st>>>(ua, da, a_stride, ub, db, b_stride, g.frame_words, g.words,
-                                                  tail_mask, g.tiles_b, partial);
+  const bool wide = all_aligned<16>(a, b) && a_stride % 4 == 0 && b_stride % 4 == 0 && g.frame_words % 4 == 0;
+  (wide ? pair_kernel<true> : pair_kernel<false>)<<<grid, kThreads, 0, st>>>(
+      ua, da, a_stride, ub, db, b_stride, g.frame_words, g.words, tail_mask, g.tiles_b, partial);
   if (const int rc = m2f::check_launch(fn)) return rc;
   const int64_t outputs = static_cast<int64_t>(da) * db + static_cast<int64_t>(da + db) * frames;
   sum_kernel<<<m2f::ceil_div(outputs, 256), 256, 0, st>>>(partial, da, db, frames, g.chunks, g.tiles_b, inter,
@@ -582,8 +485,7 @@ extern "C" int m2f_rle_decode_bits_ragged(const int32_t* positions, int64_t tota
     return m2f::fail(M2F_EINVAL, "%s: null pointer", fn);
   if (num_masks <= 0 || total < 0 || num_blocks < 0 || out_words < 0)
     return m2f::fail(M2F_EINVAL, "%s: sizes must be positive", fn);
-  if (!m2f::aligned(positions, 4) || !m2f::aligned(out, 4) || !m2f::aligned(sizes, 4) || !m2f::aligned(blocks, 4) ||
-      !m2f::aligned(offsets, 8) || !m2f::aligned(out_offsets, 8))
+  if (!all_aligned<4>(positions, out, sizes, blocks) || !all_aligned<8>(offsets, out_offsets))
     return m2f::fail(M2F_EINVAL, "%s: int32 arrays must be 4-byte aligned, int64 arrays 8-byte aligned", fn);
   if (num_blocks > kIntMax) return m2f::fail(M2F_EUNSUPPORTED, "%s: more than 2^31 - 1 column blocks", fn);
   if (num_blocks == 0) return m2f::ok();
@@ -613,9 +515,7 @@ extern "C" int m2f_bits_pair_counts_ragged(const int32_t* words, int64_t total_w
     return m2f::fail(M2F_EINVAL, "%s: null pointer", fn);
   if (num_groups <= 0 || total_words < 0 || total_a < 0 || total_b < 0 || num_tiles < 0 || num_inter < 0)
     return m2f::fail(M2F_EINVAL, "%s: sizes must be positive", fn);
-  if (!m2f::aligned(words, 4) || !m2f::aligned(tiles, 4) || !m2f::aligned(workspace, 4) ||
-      !m2f::aligned(groups, 8) || !m2f::aligned(a_offsets, 8) || !m2f::aligned(b_offsets, 8) ||
-      !m2f::aligned(inter, 8) || !m2f::aligned(area_a, 8) || !m2f::aligned(area_b, 8))
+  if (!all_aligned<4>(words, tiles, workspace) || !all_aligned<8>(groups, a_offsets, b_offsets, inter, area_a, area_b))
     return m2f::fail(M2F_EINVAL, "%s: int32 arrays must be 4-byte aligned, int64 arrays 8-byte aligned", fn);
   if (num_tiles > kIntMax) return m2f::fail(M2F_EUNSUPPORTED, "%s: more than 2^31 - 1 tiles", fn);
   if (total_words > kIntMax) return m2f::fail(M2F_EUNSUPPORTED, "%s: a buffer of more than 2^31 - 1 words", fn);

@@ -83,6 +83,11 @@ def _parse_strings(strings):
     return counts, n
 
 
+def _check_size(H, W, where=""):
+    if H <= 0 or W <= 0 or H * W >= 2 ** 31:
+        raise ValueError(f"{where}{H} x {W} pixels: sizes must be positive and fit a 32-bit count")
+
+
 def _run_ends(rles, size=None):
     """-> (positions (n,) int32 cumulative run ends, offsets (M + 1,) int64, H, W); every check of rle_to_bits."""
     rles = list(rles)
@@ -95,8 +100,7 @@ def _run_ends(rles, size=None):
     if size is None:
         raise ValueError("no mask gives the size; pass size=(H, W)")
     H, W = int(size[0]), int(size[1])
-    if H <= 0 or W <= 0 or H * W >= 2 ** 31:
-        raise ValueError(f"{H} x {W} pixels: sizes must be positive and fit a 32-bit count")
+    _check_size(H, W)
     positions, offsets = _run_ends_sized(rles, np.full(len(rles), H * W, dtype=np.int64))
     return positions, offsets, H, W
 
@@ -169,13 +173,9 @@ def rle_to_bits(rles, device=None, size=None) -> torch.Tensor:
     M = len(rles)
     if device.type != "cuda":
         return torch.from_numpy(_decode_host(positions, offsets, H, W)).to(device)
-    words = (W + 31) // 32
-    # one upload: [offsets as int32 pairs | positions]
-    host = np.concatenate((offsets.view(np.int32), positions))
-    buf = torch.from_numpy(host).to(device)
-    off = buf[:2 * (M + 1)].view(torch.int64)
-    pos = buf[2 * (M + 1):]
-    out = torch.empty((M, H, words), dtype=torch.int32, device=device)
+    dev = _upload({"offsets": offsets, "positions": positions}, device)      # one copy
+    off, pos = dev["offsets"], dev["positions"]
+    out = torch.empty((M, H, (W + 31) // 32), dtype=torch.int32, device=device)
     st = torch.cuda.current_stream(device).cuda_stream
     with torch.cuda.device(device):
         for m0 in range(0, M, _MAX_MASKS):
@@ -296,8 +296,7 @@ def _ragged_sizes(rles, sizes):
         if own is not None and given is not None and own != given:
             raise ValueError(f"mask {m} has size {own}, {given} was expected")
         H, W = own if own is not None else given
-        if H <= 0 or W <= 0 or H * W >= 2 ** 31:
-            raise ValueError(f"{H} x {W} pixels: sizes must be positive and fit a 32-bit count")
+        _check_size(H, W)
         out[m] = (H, W)
     return out
 
@@ -430,8 +429,7 @@ def _pair_plan(groups, total_words):
             b_off = np.asarray(b_off, dtype=np.int64).reshape(-1)
         except (TypeError, ValueError) as e:
             raise ValueError(f"group {g} must be (H, W, a_offsets, b_offsets)") from e
-        if H <= 0 or W <= 0 or H * W >= 2 ** 31:
-            raise ValueError(f"group {g}: {H} x {W} pixels: sizes must be positive and fit a 32-bit count")
+        _check_size(H, W, f"group {g}: ")
         fw = H * ((W + 31) // 32)
         for off in (a_off, b_off):
             if off.size and (off.min() < 0 or off.max() + fw > total_words):

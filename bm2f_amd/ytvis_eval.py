@@ -8,17 +8,18 @@ plane (``rle_to_bits``, or the head's ``pred_bits``), one ``mask_pair_counts`` l
 over all categories, and the host slices by category.  A missing frame (``None``) is a zero plane on either side, which
 is what the three branches of ``iou_seq`` (:203-217) add up to: ``i = sum |d & g|``, ``u = sum |d| + sum |g| - i``.
 
-Matching, accumulation and the summary stay on the host in numpy, vectorised over the IoU thresholds; they handle at
-most ``maxDets[-1]`` detections times a handful of objects per (video, category) and are not the hot path.
+Matching, accumulation and the summary are those of ``bm2f_amd.ap_eval``, on the host in numpy, vectorised over the
+IoU thresholds; they handle at most ``maxDets[-1]`` detections times a handful of objects per (video, category) and
+are not the hot path.
 """
 from __future__ import annotations
 
-import copy
 import json
 
 import numpy as np
 import torch
 
+from .ap_eval import VIDEO, APEvaluator, EvalResult, evaluate_units, normalize_params
 from .evaluation import instances_to_coco_json_video
 from .mask_iou import mask_pair_counts, rle_to_bits
 
@@ -75,16 +76,8 @@ class YTVISGroundTruth:
         return [c["id"] for c in self.dataset.get("categories", [])]
 
 
-class YTVISEvalResult:
-    """What ``YTVOSeval`` holds after ``evaluate()``, ``accumulate()`` and ``summarize()``: ``ious`` {(video, category):
-    (D, G) array or []}, ``evalImgs`` (one record or None per category, area range and video, in that order),
-    ``precision`` (T, R, K, A, M), ``recall`` (T, K, A, M), ``scores`` and the 12 ``stats``."""
-
-    def __init__(self, params, ious, evalImgs, precision, recall, scores, stats):
-        self.params, self.ious, self.evalImgs = params, ious, evalImgs
-        self.precision, self.recall, self.scores, self.stats = precision, recall, scores, stats
-        self.eval = {"params": params, "counts": list(precision.shape), "precision": precision, "recall": recall,
-                     "scores": scores}
+class YTVISEvalResult(EvalResult):
+    """What ``YTVOSeval`` holds after ``evaluate()``, ``accumulate()`` and ``summarize()``."""
 
 
 # -------------------------------------------------------------------------------------------------------------------
@@ -126,130 +119,6 @@ def video_pair_counts(gt, video_id, dets, device=None, pred_bits=None):
     return mask_pair_counts(a, b, W)
 
 
-# -------------------------------------------------------------------------------------------------------------------
-# host part: evaluateVid, accumulate, summarize
-# -------------------------------------------------------------------------------------------------------------------
-def _sorted_dets(dt, max_det):
-    inds = np.argsort([-d['score'] for d in dt], kind='mergesort')
-    return [dt[i] for i in inds[0:max_det]]
-
-
-def _evaluate_vid(p, gt, dt, ious_all, vidId, catId, aRng, maxDet):
-    """``evaluateVid`` (:267-345) for the ground truths ``gt`` and detections ``dt`` of one (video, category)."""
-    if len(gt) == 0 and len(dt) == 0:
-        return None
-    ignore = [1 if (g['ignore'] or (g['avg_area'] < aRng[0] or g['avg_area'] > aRng[1])) else 0 for g in gt]
-    gtind = np.argsort(ignore, kind='mergesort')                      # ignored ground truths last, stable (:289)
-    gt = [gt[i] for i in gtind]
-    dt = _sorted_dets(dt, maxDet)                                     # highest score first, stable (:291-292)
-    iscrowd = np.array([int(g['iscrowd']) for g in gt], dtype=bool)
-    ious = ious_all[:, gtind] if len(ious_all) > 0 else ious_all
-    T, G, D = len(p.iouThrs), len(gt), len(dt)
-    gtm = np.zeros((T, G))
-    dtm = np.zeros((T, D))
-    gtIg = np.array([ignore[i] for i in gtind])
-    dtIg = np.zeros((T, D))
-    if not len(ious) == 0:
-        floor = np.minimum(np.asarray(p.iouThrs, dtype=np.float64), 1 - 1e-10)   # min([t, 1 - 1e-10]) (:308)
-        gt_ids = np.array([g['id'] for g in gt])
-        rows = np.arange(T)
-        for dind, d in enumerate(dt):
-            best = floor.copy()
-            m = np.full(T, -1)
-            stopped = np.zeros(T, dtype=bool)
-            for gind in range(G):
-                # matched already and not a crowd: skip (:312); a crowd can be matched again
-                skip = (gtm[:, gind] > 0) & (not iscrowd[gind])
-                # matched to a regular ground truth and now at an ignored one: stop (:315)
-                if gtIg[gind] == 1:
-                    stopped |= ~skip & (m > -1) & (gtIg[np.maximum(m, 0)] == 0)
-                take = ~skip & ~stopped & ~(ious[dind, gind] < best)
-                best[take] = ious[dind, gind]
-                m[take] = gind
-            hit = m > -1
-            mh = m[hit]
-            dtIg[hit, dind] = gtIg[mh]
-            dtm[hit, dind] = gt_ids[mh]
-            gtm[rows[hit], mh] = d['id']
-    # unmatched detections outside the area range are ignored (:330-331)
-    a = np.array([d['avg_area'] < aRng[0] or d['avg_area'] > aRng[1] for d in dt]).reshape((1, len(dt)))
-    dtIg = np.logical_or(dtIg, np.logical_and(dtm == 0, np.repeat(a, T, 0)))
-    return {'video_id': vidId, 'category_id': catId, 'aRng': aRng, 'maxDet': maxDet,
-            'dtIds': [d['id'] for d in dt], 'gtIds': [g['id'] for g in gt], 'dtMatches': dtm, 'gtMatches': gtm,
-            'dtScores': [d['score'] for d in dt], 'gtIgnore': gtIg, 'dtIgnore': dtIg}
-
-
-def _accumulate(p, evalImgs):
-    """``accumulate`` (:347-450) with the parameters the evaluation ran with."""
-    T, R, K, A, M = len(p.iouThrs), len(p.recThrs), len(p.catIds), len(p.areaRng), len(p.maxDets)
-    precision = -np.ones((T, R, K, A, M))                             # -1 for absent settings (:366-368)
-    recall = -np.ones((T, K, A, M))
-    scores = -np.ones((T, R, K, A, M))
-    I0 = len(p.vidIds)
-    for k in range(K):
-        for a in range(A):
-            for m, maxDet in enumerate(p.maxDets):
-                E = [e for e in evalImgs[(k * A + a) * I0:(k * A + a + 1) * I0] if e is not None]
-                if len(E) == 0:
-                    continue
-                dtScores = np.concatenate([e['dtScores'][0:maxDet] for e in E])
-                inds = np.argsort(-dtScores, kind='mergesort')        # stable, as the reference (:398)
-                dtScoresSorted = dtScores[inds]
-                dtm = np.concatenate([e['dtMatches'][:, 0:maxDet] for e in E], axis=1)[:, inds]
-                dtIg = np.concatenate([e['dtIgnore'][:, 0:maxDet] for e in E], axis=1)[:, inds]
-                gtIg = np.concatenate([e['gtIgnore'] for e in E])
-                npig = np.count_nonzero(gtIg == 0)
-                if npig == 0:
-                    continue
-                tps = np.logical_and(dtm, np.logical_not(dtIg))
-                fps = np.logical_and(np.logical_not(dtm), np.logical_not(dtIg))
-                tp_sum = np.cumsum(tps, axis=1).astype(dtype=np.float32)   # float32 sums (:410-411)
-                fp_sum = np.cumsum(fps, axis=1).astype(dtype=np.float32)
-                for t, (tp, fp) in enumerate(zip(tp_sum, fp_sum)):
-                    nd = len(tp)
-                    rc = tp / npig
-                    pr = tp / (fp + tp + np.spacing(1))               # (:417)
-                    recall[t, k, a, m] = rc[-1] if nd else 0
-                    if nd:
-                        pr = np.maximum.accumulate(pr[::-1])[::-1]    # the running maximum from the right (:430-432)
-                    inds_r = np.searchsorted(rc, p.recThrs, side='left')
-                    ok = inds_r < nd                                  # the reference's loop stops at the first miss
-                    q = np.zeros((R,))
-                    ss = np.zeros((R,))
-                    q[ok] = pr[inds_r[ok]]
-                    ss[ok] = dtScoresSorted[inds_r[ok]]
-                    precision[t, :, k, a, m] = q
-                    scores[t, :, k, a, m] = ss
-    return precision, recall, scores
-
-
-def _summarize(p, precision, recall):
-    """``summarize`` (:454-504): the 12 numbers; -1 where a setting has no value."""
-    def one(ap=1, iouThr=None, areaRng='all', maxDets=100):
-        aind = [i for i, aRng in enumerate(p.areaRngLbl) if aRng == areaRng]
-        mind = [i for i, mDet in enumerate(p.maxDets) if mDet == maxDets]
-        s = precision if ap == 1 else recall
-        if iouThr is not None:
-            s = s[np.where(iouThr == p.iouThrs)[0]]
-        s = s[:, :, :, aind, mind] if ap == 1 else s[:, :, aind, mind]
-        return -1 if len(s[s > -1]) == 0 else np.mean(s[s > -1])
-
-    stats = np.zeros((12,))
-    stats[0] = one(1)
-    stats[1] = one(1, iouThr=.5, maxDets=p.maxDets[2])
-    stats[2] = one(1, iouThr=.75, maxDets=p.maxDets[2])
-    stats[3] = one(1, areaRng='small', maxDets=p.maxDets[2])
-    stats[4] = one(1, areaRng='medium', maxDets=p.maxDets[2])
-    stats[5] = one(1, areaRng='large', maxDets=p.maxDets[2])
-    stats[6] = one(0, maxDets=p.maxDets[0])
-    stats[7] = one(0, maxDets=p.maxDets[1])
-    stats[8] = one(0, maxDets=p.maxDets[2])
-    stats[9] = one(0, areaRng='small', maxDets=p.maxDets[2])
-    stats[10] = one(0, areaRng='medium', maxDets=p.maxDets[2])
-    stats[11] = one(0, areaRng='large', maxDets=p.maxDets[2])
-    return stats
-
-
 def evaluate_ytvis(gt, results, device=None, params=None, pred_bits=None, _counts=None) -> YTVISEvalResult:
     """gt: a :class:`YTVISGroundTruth`; results: the list ``instances_to_coco_json_video`` writes (``video_id``,
     ``score``, ``category_id``, ``segmentations`` with one RLE or ``None`` per frame); ``pred_bits`` optionally maps
@@ -257,91 +126,34 @@ def evaluate_ytvis(gt, results, device=None, params=None, pred_bits=None, _count
     ``device`` is where the planes are built and counted (CPU by default).  Only ``iouType="segm"`` and
     ``useCats=1`` are supported.
 
-    Reference behaviours reproduced (ytvoseval.py unless named):
-      * detection ids are ``index + 1`` in the results list (ytvos.py:249) and ``iscrowd = 0`` (ytvos.py:255);
-      * a detection's ``avg_area`` is the mean of its per-frame mask areas without the zero-area and missing frames,
-        ``l = [a for a in ann['areas'] if a]`` (ytvos.py:250-254); a ground truth's comes from its ``areas`` field
-        the same way (:100-104);
-      * a ground truth is ignored when it is a crowd (:120) or its ``avg_area`` is outside the area range (:283);
-      * detections are ordered by score and ground truths by ignore flag with the stable mergesort (:186, :289, :291);
-      * detections beyond ``maxDets[-1]`` per (video, category) are dropped (:188-189, :292);
-      * a match needs ``iou >= min(t, 1 - 1e-10)`` (:308) and a later ground truth wins ties (:318-322);
-      * a matched ground truth is skipped unless it is a crowd, which may be matched again (:312);
-      * the search stops at the first ignored ground truth once a regular one is matched (the break, :315);
-      * a matched detection takes its ground truth's ignore flag (:326); an unmatched one is ignored when its
-        ``avg_area`` is outside the area range (:330-331);
-      * ``accumulate`` sums true and false positives in float32 (:410-411), divides by ``fp + tp + np.spacing(1)``
-        (:417), makes precision monotone from the right (:430-432) and samples it with
-        ``searchsorted(side="left")`` (:434), leaving 0 beyond the last recall;
-      * precision, recall and scores are -1 for settings without ground truth (:366-368, :405), and a summary over
-        no value is -1 (:484-485); ``stats[0]`` asks for ``maxDets == 100`` whatever ``params.maxDets`` holds (:492).
-    Sequences of one video must have one length (the reference's ``zip`` would cut them to the shorter)."""
-    p = copy.deepcopy(params) if params is not None else YTVISParams()
-    if getattr(p, "iouType", "segm") != "segm" or getattr(p, "useSegm", None) is not None:
+    The rules (ordering, the ``maxDets[-1]`` cut per (video, category), matching thresholds and ties, the crowd
+    re-match, the break on ignore, float32 accumulation, the -1 conventions, the 12 statistics) are listed in
+    ``bm2f_amd.ap_eval``.  Sequences of one video must have one length (the reference's ``zip`` would cut them to the
+    shorter)."""
+    src = params if params is not None else YTVISParams()
+    if getattr(src, "iouType", "segm") != "segm" or getattr(src, "useSegm", None) is not None:
         raise NotImplementedError("only iouType='segm' is supported")
-    if not p.useCats:
-        raise NotImplementedError("only useCats=1 is supported")
-    vid_ids = p.vidIds if len(p.vidIds) else sorted(gt.video_ids())
-    cat_ids = p.catIds if len(p.catIds) else sorted(gt.category_ids())
-    p.vidIds = list(np.unique(vid_ids))
-    p.catIds = list(np.unique(cat_ids))
-    p.maxDets = sorted(p.maxDets)
-    maxDet = p.maxDets[-1]
-    known = set(gt.video_ids())
-    if any(r["video_id"] not in known for r in results):
-        raise ValueError("results name videos the ground truth does not hold")      # ytvos.py:231
-    cats = set(p.catIds)
+    p = normalize_params(VIDEO, src, gt.video_ids(), gt.category_ids(), results,
+                         "results name videos the ground truth does not hold")      # ytvos.py:231
+    if any("segmentations" not in r for r in results):
+        raise ValueError("results must hold 'segmentations'")
 
-    dets_of = {}
-    for index, r in enumerate(results):
-        if "segmentations" not in r:
-            raise ValueError("results must hold 'segmentations'")
-        dets_of.setdefault(r["video_id"], []).append((index, r))
-
-    gts_by, dts_by, ious = {}, {}, {}
-    for vidId in p.vidIds:
-        anns = gt.vid_to_anns.get(vidId, [])
-        dets = dets_of.get(vidId, [])
+    def counts_of(vidId, anns, dets):
         if _counts is not None and vidId in _counts:
-            inter, area_d, area_g = _counts[vidId]
-        elif anns or dets:
-            bits = pred_bits.get(vidId) if pred_bits else None
-            inter, area_d, area_g = video_pair_counts(gt, vidId, [r for _, r in dets], device, bits)
-        sum_g = area_g.sum(1) if anns else None
-        for j, ann in enumerate(anns):
-            if ann["category_id"] in cats:
-                gts_by.setdefault((vidId, ann["category_id"]), []).append(
-                    {"id": ann["id"], "row": j, "iscrowd": ann.get("iscrowd", 0),
-                     "ignore": bool(ann.get("iscrowd", 0)), "avg_area": _avg_area(ann["areas"])})
-        for i, (index, r) in enumerate(dets):
-            if r["category_id"] in cats:
-                areas = [int(a) if s else None for a, s in zip(area_d[i], r["segmentations"])]
-                dts_by.setdefault((vidId, r["category_id"]), []).append(
-                    {"id": index + 1, "row": i, "score": r["score"], "avg_area": _avg_area(areas)})
-        for catId in p.catIds:
-            g, d = gts_by.get((vidId, catId), []), dts_by.get((vidId, catId), [])
-            if len(g) == 0 and len(d) == 0:
-                ious[vidId, catId] = []
-                continue
-            d = _sorted_dets(d, maxDet)
-            rows_d, rows_g = [x["row"] for x in d], [x["row"] for x in g]
-            i = inter[np.ix_(rows_d, rows_g)].astype(np.float64)
-            u = area_d[rows_d].sum(1)[:, None].astype(np.float64) + sum_g[rows_g][None, :] - i if rows_g else i
-            out = np.zeros([len(d), len(g)])
-            np.divide(i, u, out=out, where=u > .0)                    # 0 where the union is empty (:216)
-            ious[vidId, catId] = out
+            return _counts[vidId]
+        return video_pair_counts(gt, vidId, dets, device, pred_bits.get(vidId) if pred_bits else None)
 
-    evalImgs = [_evaluate_vid(p, gts_by.get((vidId, catId), []), dts_by.get((vidId, catId), []), ious[vidId, catId],
-                              vidId, catId, aRng, maxDet)
-                for catId in p.catIds for aRng in p.areaRng for vidId in p.vidIds]
-    precision, recall, scores = _accumulate(p, evalImgs)
-    return YTVISEvalResult(p, ious, evalImgs, precision, recall, scores, _summarize(p, precision, recall))
+    def dt_area(r, areas):
+        return _avg_area([int(a) if s else None for a, s in zip(areas, r["segmentations"])])
+
+    return evaluate_units(p, VIDEO, gt.vid_to_anns, results, counts_of, lambda ann: _avg_area(ann["areas"]), dt_area,
+                          crowd_iou=False, result_cls=YTVISEvalResult)
 
 
 # -------------------------------------------------------------------------------------------------------------------
 # the evaluator
 # -------------------------------------------------------------------------------------------------------------------
-class YTVISEvaluator:
+class YTVISEvaluator(APEvaluator):
     """The reference's ``YTVISEvaluator`` (ytvis_eval.py:27-253) without detectron2: ``reset()``, ``process(inputs,
     outputs)`` per video and ``evaluate()``.
 
@@ -352,20 +164,12 @@ class YTVISEvaluator:
 
     def __init__(self, ground_truth, thing_dataset_id_to_contiguous_id=None, class_names=None, device=None,
                  params=None):
-        self.gt = ground_truth if isinstance(ground_truth, YTVISGroundTruth) else YTVISGroundTruth(ground_truth)
-        self.id_map = thing_dataset_id_to_contiguous_id
-        self.class_names = class_names
-        self.device = device
-        self.params = params
-        self.reset()
+        gt = ground_truth if isinstance(ground_truth, YTVISGroundTruth) else YTVISGroundTruth(ground_truth)
+        super().__init__(gt, thing_dataset_id_to_contiguous_id, class_names, device, params)
 
     def reset(self):
-        self._predictions = []
+        super().reset()
         self._counts = {}
-
-    @property
-    def results(self):
-        return self._predictions
 
     def process(self, inputs, outputs):
         prediction = instances_to_coco_json_video(inputs, outputs)
@@ -400,15 +204,4 @@ class YTVISEvaluator:
             return {}
         self.last = evaluate_ytvis(self.gt, self._mapped(), device=self.device, params=self.params,
                                    _counts=self._counts)
-        metrics = ["AP", "AP50", "AP75", "APs", "APm", "APl", "AR1", "AR10"]
-        stats = self.last.stats
-        res = {m: float(stats[i] * 100 if stats[i] >= 0 else "nan") for i, m in enumerate(metrics)}
-        names = self.class_names
-        if names is not None and len(names) > 1:
-            precisions = self.last.precision
-            assert len(names) == precisions.shape[2]
-            for idx, name in enumerate(names):
-                pr = precisions[:, :, idx, 0, -1]
-                pr = pr[pr > -1]
-                res["AP-" + "{}".format(name)] = float(np.mean(pr) * 100) if pr.size else float("nan")
-        return {"segm": res}
+        return {"segm": self._derive(self.last)}

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from bm2f_amd import (VideoMaskFormerInference, YTVISEvaluator, YTVISGroundTruth, YTVISParams, evaluate_ytvis,
-                      mask_pair_counts, pack_mask_bits, rle_encode, rle_to_bits, string_to_counts)
+                      mask_pair_counts, pack_mask_bits, rle_encode, rle_to_bits, rle_to_bits_ragged, string_to_counts)
 from bm2f_amd.mask_iou import pair_tiles
 from ytvis_eval_cases import CONFIGS, FIELDS, flatten, load_fixture
 
@@ -82,6 +82,22 @@ def test_decode_uncompressed_and_all_none(device):
     assert tuple(z.shape) == (2, 7, 2) and int(z.abs().sum()) == 0
     with pytest.raises(ValueError):
         rle_to_bits([{"size": [7, 33], "counts": [5, 5]}], device=device)
+
+
+def test_decode_uniform_equals_ragged(device):
+    """The two decode kernels share one column decoder: the same eight masks (the 9 x 40 run edges, three 7 x 33 and a
+    missing 7 x 33) through rle_to_bits, one size per call, and through one rle_to_bits_ragged call, word for word."""
+    edges = [_single(9, 40, (7, 31), (8, 31), (0, 32), (1, 32), (8, 5), (0, 6)),
+             _single(9, 40, (8, 31), (8, 32), (8, 39), (8, 0)), _single(9, 40, (0, 0)), _single(9, 40, (8, 39))]
+    small = rle_encode(_rand((3, 7, 33), 0.5, 9))
+    small.insert(1, None)
+    rles = rle_encode(torch.stack(edges)) + small
+    words, off, hw = rle_to_bits_ragged(rles, device=device, sizes=[None] * 5 + [(7, 33)] + [None] * 2)
+    assert words.device.type == "cuda" and [tuple(s) for s in hw] == [(9, 40)] * 4 + [(7, 33)] * 4
+    uniform = [*rle_to_bits(rles[:4], device=device), *rle_to_bits(rles[4:], device=device, size=(7, 33))]
+    for m, plane in enumerate(uniform):
+        assert torch.equal(words[off[m]:off[m] + plane.numel()], plane.reshape(-1)), m
+    assert int(uniform[5].abs().sum()) == 0
 
 
 def _dense(a, b):

@@ -5,6 +5,8 @@ import os
 
 import numpy as np
 
+from coco_eval_cases import flatten as _flatten
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 GT_JSON = os.path.join(GOLDEN, "ytvis_eval_gt.json")
 RESULTS_JSON = os.path.join(GOLDEN, "ytvis_eval_results.json")
@@ -19,42 +21,7 @@ FIELDS = ("iou_keys", "iou_shapes", "iou_values", "img_none", "img_meta", "img_n
 
 def flatten(ious, eval_imgs, precision, recall, scores, stats, num_thresholds):
     """-> {field: array}; every field of every evalImgs record is kept, concatenated over the records."""
-    keys = sorted(ious.keys())
-    shapes, values = [], []
-    for k in keys:
-        v = ious[k]
-        if isinstance(v, list) and len(v) == 0:
-            shapes.append((-1, -1))                                   # the reference's [] for an empty pair
-        else:
-            v = np.asarray(v, dtype=np.float64)
-            shapes.append(v.shape)
-            values.append(v.reshape(-1))
-    live = [e for e in eval_imgs if e is not None]
-    T = num_thresholds
-
-    def cat(field, axis, empty):
-        parts = [np.asarray(e[field], dtype=np.float64) for e in live]
-        return np.concatenate(parts, axis=axis) if parts else empty
-
-    return {
-        "iou_keys": np.asarray(keys, dtype=np.int64).reshape(-1, 2),
-        "iou_shapes": np.asarray(shapes, dtype=np.int64).reshape(-1, 2),
-        "iou_values": np.concatenate(values) if values else np.zeros(0),
-        "img_none": np.asarray([e is None for e in eval_imgs]),
-        "img_meta": np.asarray([[e["video_id"], e["category_id"], e["aRng"][0], e["aRng"][1], e["maxDet"]]
-                                for e in live], dtype=np.float64).reshape(-1, 5),
-        "img_nd": np.asarray([len(e["dtIds"]) for e in live], dtype=np.int64),
-        "img_ng": np.asarray([len(e["gtIds"]) for e in live], dtype=np.int64),
-        "dtIds": cat("dtIds", 0, np.zeros(0)),
-        "gtIds": cat("gtIds", 0, np.zeros(0)),
-        "dtMatches": cat("dtMatches", 1, np.zeros((T, 0))),
-        "gtMatches": cat("gtMatches", 1, np.zeros((T, 0))),
-        "dtScores": cat("dtScores", 0, np.zeros(0)),
-        "gtIgnore": cat("gtIgnore", 0, np.zeros(0)),
-        "dtIgnore": cat("dtIgnore", 1, np.zeros((T, 0))),
-        "precision": np.asarray(precision), "recall": np.asarray(recall), "scores": np.asarray(scores),
-        "stats": np.asarray(stats, dtype=np.float64),
-    }
+    return _flatten(ious, eval_imgs, precision, recall, scores, stats, num_thresholds, id_key="video_id")
 
 
 def load_fixture():
