@@ -13,6 +13,8 @@ from .coco_eval import (COCOEvalResult, COCOEvaluator, COCOGroundTruth, COCOPara
                         evaluate_coco)
 from .mask_iou import (mask_iou, mask_pair_counts, mask_pair_counts_ragged, rle_to_bits,  # noqa: F401
                        rle_to_bits_ragged)
+from .polygon import (ann_to_rle, convert_polygons_to_rle, polygon_crossings, polygons_to_bits,  # noqa: F401
+                      polygons_to_bits_ragged, polygons_to_rle)
 from .rle import counts_to_string, rle_area, rle_decode, rle_encode, string_to_counts  # noqa: F401
 from .swin import D2SwinTransformer, SwinTransformer, window_attention  # noqa: F401
 from .video_criterion import (VideoHungarianMatcherProj, VideoHungarianMatcherProjPair,  # noqa: F401

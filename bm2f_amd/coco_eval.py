@@ -16,9 +16,13 @@ The mask work is batched over images of different sizes: the images are cut into
 ``batch_bytes``, and a batch costs one upload, one launch of the ragged RLE decoder, one call of the ragged pair
 counts and one device-to-host copy (``mask_iou.rle_pair_counts_ragged``), whatever the number of images in it.
 
-Ground-truth segmentations must be RLE (compressed, or uncompressed as COCO stores crowds).  Polygons raise
-``NotImplementedError``: they have to be converted to RLE once beforehand with the rasteriser the numbers are to be
-compared with; a different rasteriser here would change AP silently.
+Ground-truth segmentations are RLE (compressed, or uncompressed as COCO stores crowds).  Polygons raise
+``NotImplementedError`` by default, because a different rasteriser would change AP silently: convert the file once
+beforehand (``bm2f_amd.polygon.convert_polygons_to_rle``, or the rasteriser the numbers are to be compared with), or
+pass ``polygons="rasterize"``.  Then a batch's RLE masks and polygon annotations go into one ragged buffer
+(``polygon.pair_counts_ragged``): still one upload, one copy and a number of launches that does not depend on the
+batch.  The rasteriser is ``bm2f_amd.polygon``'s restatement of ``rleFrPoly``; it has not been run against
+pycocotools itself.  A batch without polygons takes the RLE path unchanged.
 """
 from __future__ import annotations
 
@@ -30,6 +34,7 @@ import numpy as np
 from .ap_eval import IMAGE, APEvaluator, EvalResult, evaluate_units, normalize_params
 from .evaluation import instances_to_coco_json
 from .mask_iou import MAX_RAGGED_WORDS, rle_pair_counts_ragged
+from .polygon import check_annotation, is_polygon, pair_counts_ragged
 
 DEFAULT_BATCH_BYTES = 64 << 20
 """Bit planes per batch.  A COCO val image with 100 detections and 7 ground truths is ~107 planes of ~38 KB, about
@@ -56,9 +61,13 @@ class COCOParams:
 class COCOGroundTruth:
     """A COCO instances file (or the dict it holds): ``images``, ``annotations`` and ``categories`` indexed as
     ``pycocotools.coco.COCO`` does.  A segmentation is a compressed or an uncompressed RLE dict; a polygon raises
-    NotImplementedError (see the module docstring)."""
+    NotImplementedError with ``polygons="refuse"`` (the default) and is kept, to be rasterised by the evaluation, with
+    ``polygons="rasterize"`` (see the module docstring)."""
 
-    def __init__(self, dataset):
+    def __init__(self, dataset, polygons="refuse"):
+        if polygons not in ("refuse", "rasterize"):
+            raise ValueError("polygons must be 'refuse' or 'rasterize'")
+        self.polygons = polygons
         if isinstance(dataset, (str, bytes)) or hasattr(dataset, "__fspath__"):
             with open(dataset) as f:
                 dataset = json.load(f)
@@ -72,7 +81,7 @@ class COCOGroundTruth:
         self.img_to_anns = {}
         for ann in self.anns:
             seg = ann.get("segmentation")
-            if seg is not None and not isinstance(seg, dict):
+            if seg is not None and not isinstance(seg, dict) and polygons == "refuse":
                 raise NotImplementedError(
                     f"annotation {ann.get('id')} holds a polygon segmentation: convert the file to RLE once "
                     "beforehand (polygons are not rasterised here)")
@@ -102,6 +111,9 @@ def _check_segm(gt, img_id, dets, anns):
     for what, items in (("result", dets), ("annotation", anns)):
         for r in items:
             seg = r.get("segmentation")
+            if what == "annotation" and gt.polygons == "rasterize" and is_polygon(seg):
+                check_annotation(seg, f"annotation {r.get('id')}")
+                continue
             if not isinstance(seg, dict) or "size" not in seg or "counts" not in seg:
                 raise ValueError(f"a {what} of image {img_id} has no RLE segmentation")
             if [int(v) for v in seg["size"]] != size:
@@ -136,15 +148,22 @@ def _segm_counts(gt, img_ids, dets_of, device, batch_bytes):
     for img_id in img_ids:                                            # every check before the first launch
         _check_segm(gt, img_id, dets_of.get(img_id, []), gt.img_to_anns.get(img_id, []))
     for batch in image_batches(gt, img_ids, dets_of, batch_bytes):
-        rles, groups = [], []
+        rles, groups, sizes, names = [], [], [], []
         for img_id in batch:
             dets, anns = dets_of.get(img_id, []), gt.img_to_anns.get(img_id, [])
             n0 = len(rles)
             rles += [r["segmentation"] for r in dets] + [a["segmentation"] for a in anns]
             img = gt.imgs[img_id]
-            groups.append((int(img["height"]), int(img["width"]), np.arange(n0, n0 + len(dets)),
+            size = (int(img["height"]), int(img["width"]))
+            sizes += [None] * len(dets) + [size if is_polygon(a["segmentation"]) else None for a in anns]
+            names += [None] * len(dets) + [f"annotation {a.get('id')}" for a in anns]
+            groups.append((size[0], size[1], np.arange(n0, n0 + len(dets)),
                            np.arange(n0 + len(dets), n0 + len(dets) + len(anns))))
-        for img_id, c in zip(batch, rle_pair_counts_ragged(rles, groups, device=device)):
+        if any(s is not None for s in sizes):                         # polygon ground truth in this batch
+            batch_counts = pair_counts_ragged(rles, groups, device=device, sizes=sizes, names=names)
+        else:
+            batch_counts = rle_pair_counts_ragged(rles, groups, device=device)
+        for img_id, c in zip(batch, batch_counts):
             counts[img_id] = c
     return counts
 
@@ -213,13 +232,15 @@ class COCOEvaluator(APEvaluator):
     ``process`` takes detectron2's pairs: ``inputs[i]["image_id"]`` and ``outputs[i]["instances"]``, the dict of
     :class:`MaskFormerInference` (``instance_rle=True`` or plain masks), written with ``instances_to_coco_json``.
     ``results`` is the accumulated ``coco_instances_results.json`` list with the head's contiguous category ids;
-    ``evaluate`` maps them back through ``thing_dataset_id_to_contiguous_id`` (instance_evaluation.py:52-70)."""
+    ``evaluate`` maps them back through ``thing_dataset_id_to_contiguous_id`` (instance_evaluation.py:52-70).
+    ``polygons`` is passed to :class:`COCOGroundTruth` when ``ground_truth`` is not one already."""
 
     def __init__(self, ground_truth, thing_dataset_id_to_contiguous_id=None, class_names=None, device=None,
-                 params=None, tasks=("segm",), batch_bytes=DEFAULT_BATCH_BYTES):
+                 params=None, tasks=("segm",), batch_bytes=DEFAULT_BATCH_BYTES, polygons="refuse"):
         self.tasks = tuple(tasks)
         self.batch_bytes = batch_bytes
-        gt = ground_truth if isinstance(ground_truth, COCOGroundTruth) else COCOGroundTruth(ground_truth)
+        gt = (ground_truth if isinstance(ground_truth, COCOGroundTruth)
+              else COCOGroundTruth(ground_truth, polygons=polygons))
         super().__init__(gt, thing_dataset_id_to_contiguous_id, class_names, device, params)
 
     def reset(self):

@@ -521,6 +521,21 @@ def mask_pair_counts_ragged(words, groups):
     return _split_counts(out.cpu().numpy(), desc)                     # the one copy
 
 
+def _groups_by_offset(groups, hw, out_offsets):
+    """Groups ``(H, W, a_masks, b_masks)`` of indices into a batch of masks of sizes ``hw`` at ``out_offsets`` ->
+    the ``(H, W, a_offsets, b_offsets)`` of mask_pair_counts_ragged, with the checks of the indices."""
+    by_offset = []
+    for g, (H, W, ia, ib) in enumerate(groups):
+        ia, ib = np.asarray(ia, dtype=np.int64).reshape(-1), np.asarray(ib, dtype=np.int64).reshape(-1)
+        for idx in (ia, ib):
+            if idx.size and (idx.min() < 0 or idx.max() >= hw.shape[0]):
+                raise ValueError(f"group {g} names masks outside the batch")
+            if idx.size and ((hw[idx, 0] != int(H)) | (hw[idx, 1] != int(W))).any():
+                raise ValueError(f"group {g}: a mask's size is not the group's {int(H)} x {int(W)}")
+        by_offset.append((H, W, out_offsets[ia], out_offsets[ib]))
+    return by_offset
+
+
 def rle_pair_counts_ragged(rles, groups, device=None, sizes=None):
     """:func:`rle_to_bits_ragged` and :func:`mask_pair_counts_ragged` of one batch with a single upload: ``groups``
     holds ``(H, W, a_masks, b_masks)`` with *indices into* ``rles`` in place of word offsets.  -> the per-group
@@ -534,16 +549,7 @@ def rle_pair_counts_ragged(rles, groups, device=None, sizes=None):
     if not rles:
         return [(np.zeros((0, 0), np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64)) for _ in groups]
     hw, out_offsets, total, dtables = _decode_plan(rles, sizes)
-    by_offset = []
-    for g, (H, W, ia, ib) in enumerate(groups):
-        ia, ib = np.asarray(ia, dtype=np.int64).reshape(-1), np.asarray(ib, dtype=np.int64).reshape(-1)
-        for idx in (ia, ib):
-            if idx.size and (idx.min() < 0 or idx.max() >= len(rles)):
-                raise ValueError(f"group {g} names masks outside the batch")
-            if idx.size and ((hw[idx, 0] != int(H)) | (hw[idx, 1] != int(W))).any():
-                raise ValueError(f"group {g}: a mask's size is not the group's {int(H)} x {int(W)}")
-        by_offset.append((H, W, out_offsets[ia], out_offsets[ib]))
-    desc, ptables, num_tiles = _pair_plan(by_offset, total)
+    desc, ptables, num_tiles = _pair_plan(_groups_by_offset(groups, hw, out_offsets), total)
     if device.type != "cuda":
         words = rle_to_bits_ragged(rles, device, sizes)[0]
         return _pair_counts_ragged_host(words.numpy(), desc, ptables)

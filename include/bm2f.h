@@ -789,6 +789,45 @@ int m2f_bits_pair_counts_ragged(const int32_t* words, int64_t total_words, const
                                 int64_t* area_a, int64_t* area_b, void* workspace, int64_t workspace_bytes,
                                 void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * COCO polygons -> bit planes (bm2f_amd/polygon.py; the definition, a restatement of rleFrPoly of
+ * pycocotools' maskApi.c, is in DESIGN.md §3).  A polygon's mask is given by its crossings: positions
+ * p = c * H + y in the column-major order, pixel q being set when an odd number of them is <= q.
+ *
+ *   m2f_poly_crossings    one thread per kept crossing of a batch of polygons.  edges (E,
+ *                         M2F_POLY_EDGE_FIELDS) int32 = kind, xs, ys, steps, c0, H, W, polygon: the edge's
+ *                         oriented start in fifths of a pixel (flat, kind 0: the smaller x; steep, kind 1: the
+ *                         smaller y), its number of steps max(|dx|, |dy|), the first kept column c0 and the
+ *                         image size and index of its polygon; slopes (E) fp64 = dy / dx (flat) or dx / dy
+ *                         (steep), divided by the caller; starts (E) int64 = the running sum of the edges'
+ *                         crossing counts, non-decreasing, starts[0] = 0; total = their sum.  Crossing j of
+ *                         edge e is at the column c = c0 + j, u = 5 c + 2, and its row is
+ *                         clamp(ceil((v - 2) / 5), 0, H) with
+ *                           flat:  v = min(y(u - xs), y(u - xs + 1)),  y(t) = trunc(ys + s * t + 0.5)
+ *                           steep: v = ys + t, t the last step in [0, steps] with x(t) <= u (s > 0) or
+ *                                  x(t) >= u + 1 (s < 0), found by bisection, x(t) = trunc(xs + s * t + 0.5)
+ *                         in fp64 with every operation rounded on its own (no FMA).  A row of kind 2 is one
+ *                         "crossing" at H * W, the sentinel that closes a polygon.  keys (total) int64 =
+ *                         (polygon << 32) | p: sorting them orders every polygon's positions.  No atomics, no
+ *                         loop over an edge's length.
+ *   m2f_poly_decode_bits_ragged   annotation a is the OR of the polygons part_offsets[a] .. part_offsets[a + 1]
+ *                         (part_offsets (A + 1) int64, clamped to [0, num_polys]; none: a zero plane); polygon q
+ *                         owns the sorted positions[pos_offsets[q] : pos_offsets[q + 1]] (pos_offsets
+ *                         (num_polys + 1) int64, clamped to [0, total]).  sizes, out_offsets, blocks, out and
+ *                         out_words as m2f_rle_decode_bits_ragged, per annotation: every word of every plane
+ *                         is stored exactly once, tail bits zero, padding words are not written.
+ * Null pointers, negative sizes or misaligned pointers give M2F_EINVAL; more than 2^31 - 1 crossings or
+ * table rows M2F_EUNSUPPORTED; all before any HIP call.  The kernels check every index they take from a table
+ * against the sizes passed by value.
+ * ------------------------------------------------------------------------------------------- */
+enum { M2F_POLY_EDGE_FIELDS = 8 };
+int m2f_poly_crossings(const int32_t* edges, const double* slopes, const int64_t* starts, int64_t num_edges,
+                       int64_t total, int64_t* keys, void* stream);
+int m2f_poly_decode_bits_ragged(const int32_t* positions, int64_t total, const int64_t* pos_offsets,
+                                int64_t num_polys, const int64_t* part_offsets, int num_anns, const int32_t* sizes,
+                                const int64_t* out_offsets, const int32_t* blocks, int64_t num_blocks, int32_t* out,
+                                int64_t out_words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
