@@ -13,6 +13,10 @@ from .coco_eval import (COCOEvalResult, COCOEvaluator, COCOGroundTruth, COCOPara
                         evaluate_coco)
 from .mask_iou import (mask_iou, mask_pair_counts, mask_pair_counts_ragged, rle_to_bits,  # noqa: F401
                        rle_to_bits_ragged)
+from .label_counts import label_pair_counts, label_pair_counts_ragged  # noqa: F401
+from .panoptic_eval import (COCOPanopticEvaluator, PanopticGroundTruth, PQStat, evaluate_panoptic,  # noqa: F401
+                            id2rgb, pq_from_counts, rgb2id)
+from .sem_seg_eval import SemSegEvaluator, evaluate_sem_seg, sem_seg_metrics  # noqa: F401
 from .polygon import (ann_to_rle, convert_polygons_to_rle, polygon_crossings, polygons_to_bits,  # noqa: F401
                       polygons_to_bits_ragged, polygons_to_rle)
 from .rle import counts_to_string, rle_area, rle_decode, rle_encode, string_to_counts  # noqa: F401

@@ -790,6 +790,43 @@ int m2f_bits_pair_counts_ragged(const int32_t* words, int64_t total_words, const
                                 void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Label-pair counts of a ragged batch of images (semantic mIoU and panoptic PQ, bm2f_amd/label_counts.py).
+ * Image i has P_i pixels and two label planes: a (ground truth; a_bytes 1 = uint8, 2 = int16, 4 = int32) at element
+ * offset a_off of the flat buffer `a` (a_elems elements) and b (prediction; b_bytes 1 = uint8, 2 = int16, 4 = int32,
+ * 8 = int64) at b_off of `b`.  Offsets are in elements and need not be aligned; aligned parts are read 8 or 16
+ * bytes at a time when the buffer starts on 16 bytes.  Such a load stays inside an aligned 16-byte block that holds
+ * at least one byte of the plane; the neighbours' elements it brings along are masked.
+ *
+ *   images (G, M2F_LABEL_IMAGE_FIELDS) int64 = a_off, b_off, pixels, rows, cols, out_off, id_off, id_count.
+ *       The image's table is rows x cols int64 counters, row-major, at out + out_off; rows * cols < 2^31.
+ *       Several images may name one out_off (of equal cols): the kernel adds, the caller zeroes `out` and `bad`.
+ *   row of a value v of a:
+ *       id_count < 0 (direct)   v == ignore (when has_ignore) -> rows - 1; else v in [0, rows - 1) -> v;
+ *                               anything else adds 1 to bad[i] and the pixel is not counted.
+ *       id_count >= 0 (id list) ids[id_off .. id_off + id_count) int32, sorted ascending without repeats,
+ *                               id_count <= min(M2F_LABEL_MAX_IDS, rows - 1): v found at index j -> j, v not in
+ *                               the list -> rows - 1.  Any int32 id works.
+ *   column of a value w of b:   w in [0, cols) -> w; anything else adds 1 to bad[i], the pixel is not counted.
+ *   blocks (num_blocks, 2) int32 = (image, chunk), one row per workgroup: image i has ceil(n_i /
+ *       M2F_LABEL_CHUNK_VECS) rows with n_i = ceil((a_off % M2F_LABEL_VEC + P_i) / M2F_LABEL_VEC), none when
+ *       P_i = 0.
+ *   path 0: tables are privatised in LDS when max_bins, the largest rows * cols of the batch, is at most
+ *       M2F_LABEL_LDS_BINS, else added with wave-merged global atomics; 1 forces LDS (M2F_EINVAL when max_bins is
+ *       beyond it), 2 forces the global path.  Either way the counts are exact integers, the same on every run.
+ * One launch whatever G is.  Null pointers, negative sizes, unknown widths or paths, or misaligned buffers give
+ * M2F_EINVAL; more than 2^31 - 1 table rows or counters M2F_EUNSUPPORTED; all before any HIP call.  The kernel checks
+ * every field it takes from a table against the sizes passed by value.
+ * ------------------------------------------------------------------------------------------- */
+enum { M2F_LABEL_IMAGE_FIELDS = 8, M2F_LABEL_VEC = 8, M2F_LABEL_CHUNK_VECS = 8192, M2F_LABEL_LDS_BINS = 24576,
+       M2F_LABEL_MAX_IDS = 1024 };
+int m2f_label_counts_geometry(int* vec, int* chunk_vecs, int* lds_bins, int* max_ids);
+int m2f_label_pair_counts_ragged(const void* a, int a_bytes, int64_t a_elems, const void* b, int b_bytes,
+                                 int64_t b_elems, const int64_t* images, int num_images, const int32_t* ids,
+                                 int64_t total_ids, const int32_t* blocks, int64_t num_blocks, int has_ignore,
+                                 int ignore, int64_t max_bins, int path, int64_t* out, int64_t out_len, int64_t* bad,
+                                 void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * COCO polygons -> bit planes (bm2f_amd/polygon.py; the definition, a restatement of rleFrPoly of
  * pycocotools' maskApi.c, is in DESIGN.md §3).  A polygon's mask is given by its crossings: positions
  * p = c * H + y in the column-major order, pixel q being set when an odd number of them is <= q.
