@@ -13,6 +13,8 @@ import ctypes
 import os
 import threading
 
+import torch
+
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libbm2f.so")
 _lock = threading.Lock()
 _lib = None
@@ -127,6 +129,10 @@ _SIGNATURES = {
 }
 
 
+# include/bm2f.h: ``enum { M2F_F32 = 0, M2F_F16 = 1, M2F_BF16 = 2 };`` (tests/test_capi.py compares the two)
+DTYPE_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
 class NativeError(RuntimeError):
     """A nonzero status returned by libbm2f (message from ``m2f_last_error``)."""
 
@@ -176,15 +182,55 @@ def call(name: str, *args) -> None:
         raise NativeError(f"{name} failed (code {rc}): {msg}")
 
 
+# What every wrapper puts between a tensor and call(): scalars go in as plain Python numbers (``argtypes``, set from
+# _SIGNATURES in load(), converts them to the declared width), so a wrong kind in that table is a wrong register.
+def stream(x) -> int:
+    """The raw handle of the current stream on the device of ``x``, a tensor or a ``torch.device``."""
+    return torch.cuda.current_stream(getattr(x, "device", x)).cuda_stream
+
+
+def dtype_code(dtype, what: str) -> int:
+    """M2F_F32 / M2F_F16 / M2F_BF16 for a torch dtype; RuntimeError naming ``what`` for any other."""
+    try:
+        return DTYPE_CODES[dtype]
+    except KeyError:
+        raise RuntimeError(f"{what}: unsupported dtype {dtype}") from None
+
+
+def ptr(t):
+    """``t.data_ptr()``, NULL for ``None`` (an optional operand)."""
+    return None if t is None else t.data_ptr()
+
+
+def ptr_or_null(t):
+    """``t.data_ptr()``, NULL for an empty tensor: for the entry points that take NULL only with a zero count."""
+    return t.data_ptr() if t.numel() else None
+
+
+_OUT = {"i": ctypes.c_int, "l": ctypes.c_int64}
+
+
+def query(name: str, *args, outs: str = "l"):
+    """Call an entry point whose trailing parameters are outputs, ``int*`` ("i") or ``int64_t*`` ("l") per letter
+    of ``outs``, and return their values: the value itself for one output, else a tuple."""
+    vals = [_OUT[k]() for k in outs]
+    call(name, *args, *(ctypes.byref(v) for v in vals))
+    return vals[0].value if len(vals) == 1 else tuple(v.value for v in vals)
+
+
+def workspace(name: str, *args, device, dtype=torch.uint8, floor: int = 0, unit: int = 1):
+    """The scratch tensor of a ``*_workspace`` query: ``max(n, floor) // unit`` elements of ``dtype`` for the ``n``
+    (bytes or words, see bm2f.h) that ``name(*args, &n)`` reports."""
+    return torch.empty(max(query(name, *args), floor) // unit, dtype=dtype, device=device)
+
+
 def set_option(name: str, value: int) -> None:
     """m2f_set_option: a geometry / engine override (value < 0 restores the default)."""
     call("m2f_set_option", name.encode(), int(value))
 
 
 def get_option(name: str) -> int:
-    v = ctypes.c_int64()
-    call("m2f_get_option", name.encode(), ctypes.byref(v))
-    return v.value
+    return query("m2f_get_option", name.encode())
 
 
 @contextlib.contextmanager

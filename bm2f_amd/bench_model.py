@@ -27,7 +27,6 @@ from .transformer_decoder import MultiScaleMaskedTransformerDecoder
 
 PIXEL_MEAN = (123.675, 116.280, 103.530)
 PIXEL_STD = (58.395, 57.120, 57.375)
-_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}   # M2F_F32 / M2F_F16 / M2F_BF16
 
 
 class FrozenBNConv(nn.Module):
@@ -98,11 +97,10 @@ class _BiasAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, r, bias, nout):
         from . import _native
-        code = _CODE[x.dtype]
+        code = _native.dtype_code(x.dtype, "bench backbone")
         cl = 0 if x.is_contiguous() else 1
-        _native.call("m2f_bias_act_nchw", x.data_ptr(), r.data_ptr() if r is not None else None,
-                     bias.data_ptr(), x.shape[0], x.shape[1], x.shape[2] * x.shape[3], code, cl,
-                     torch.cuda.current_stream(x.device).cuda_stream)
+        _native.call("m2f_bias_act_nchw", x.data_ptr(), _native.ptr(r), bias.data_ptr(), x.shape[0], x.shape[1],
+                     x.shape[2] * x.shape[3], code, cl, _native.stream(x))
         ctx.mark_dirty(x)
         ctx.save_for_backward(x)
         ctx.has_r = r is not None
@@ -122,7 +120,7 @@ class _BiasAct(torch.autograd.Function):
             g = torch.empty_like(y, memory_format=torch.preserve_format)   # elementwise: any dense layout
             ptrs = (ctypes.c_void_p * len(gs))(*[t.data_ptr() for t in gs])
             _native.call("m2f_relu_bwd_sum", ptrs, len(gs), y.data_ptr(), g.data_ptr(), y.numel(),
-                         _CODE[y.dtype], torch.cuda.current_stream(y.device).cuda_stream)
+                         _native.dtype_code(y.dtype, "bench backbone"), _native.stream(y))
         else:
             g = torch.ops.aten.threshold_backward(sum(gs), y, 0)
         return g, (g if ctx.has_r else None), None, None
@@ -161,7 +159,7 @@ class _MaxPool3s2(torch.autograd.Function):
         y = torch.empty(N, C, OH, OW, device=x.device, dtype=x.dtype)
         win = torch.empty(N, C, OH, OW, device=x.device, dtype=torch.uint8)
         _native.call("m2f_maxpool3s2_fwd", x.data_ptr(), y.data_ptr(), win.data_ptr(), N * C, H, W,
-                     _CODE[x.dtype], torch.cuda.current_stream(x.device).cuda_stream)
+                     _native.dtype_code(x.dtype, "bench backbone"), _native.stream(x))
         ctx.save_for_backward(win)
         ctx.in_shape = x.shape
         return y
@@ -174,7 +172,7 @@ class _MaxPool3s2(torch.autograd.Function):
         N, C, H, W = ctx.in_shape
         gx = torch.empty(ctx.in_shape, device=g.device, dtype=g.dtype)
         _native.call("m2f_maxpool3s2_bwd", g.data_ptr(), win.data_ptr(), gx.data_ptr(), N * C, H, W,
-                     _CODE[g.dtype], torch.cuda.current_stream(g.device).cuda_stream)
+                     _native.dtype_code(g.dtype, "bench backbone"), _native.stream(g))
         return gx
 
 
@@ -189,7 +187,7 @@ class _MaxPool3s2NHWC(torch.autograd.Function):
         y = torch.empty(N, OH, OW, C, device=x.device, dtype=x.dtype).permute(0, 3, 1, 2)
         win = torch.empty(N, OH, OW, C, device=x.device, dtype=torch.uint8)
         _native.call("m2f_maxpool3s2_nhwc", 0, x.data_ptr(), y.data_ptr(), win.data_ptr(), N, H, W, C,
-                     _CODE[x.dtype], torch.cuda.current_stream(x.device).cuda_stream)
+                     _native.dtype_code(x.dtype, "bench backbone"), _native.stream(x))
         ctx.save_for_backward(win)
         ctx.in_shape = x.shape
         return y
@@ -202,7 +200,7 @@ class _MaxPool3s2NHWC(torch.autograd.Function):
         g = grad.contiguous(memory_format=torch.channels_last)
         gx = torch.empty(N, H, W, C, device=g.device, dtype=g.dtype).permute(0, 3, 1, 2)
         _native.call("m2f_maxpool3s2_nhwc", 1, g.data_ptr(), gx.data_ptr(), win.data_ptr(), N, H, W, C,
-                     _CODE[g.dtype], torch.cuda.current_stream(g.device).cuda_stream)
+                     _native.dtype_code(g.dtype, "bench backbone"), _native.stream(g))
         return gx
 
 

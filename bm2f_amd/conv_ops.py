@@ -10,8 +10,6 @@ else uses ``F.conv2d``.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 import torch.nn.functional as F
 from torch.autograd import Function
@@ -26,21 +24,8 @@ from . import _native
 WGRAD3 = "tn"   # 3x3 weight gradient: "tn" (x3 TN GEMMs per tap) or "miopen"; set by tools / tests
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _workspace(N, Ci, Co, H, W, k, device):
-    b = ctypes.c_int64(0)
-    _native.call("m2f_conv_f32x3_workspace", N, Ci, Co, H, W, k, ctypes.byref(b))
-    return torch.empty(max(b.value, 16), device=device, dtype=torch.uint8)
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
-_DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}   # M2F_F32 / M2F_F16 / M2F_BF16
+    return _native.workspace("m2f_conv_f32x3_workspace", N, Ci, Co, H, W, k, device=device, floor=16)
 
 
 def _act16(x):
@@ -66,13 +51,13 @@ class Conv2dX3(Function):
         ctx.nhwc = 0
         if x.dtype == torch.float32:
             x = x.contiguous()
-            _native.call("m2f_conv_f32x3", x.data_ptr(), weight.data_ptr(), _ptr(bias), out.data_ptr(), N, Ci, Co, H,
-                         W, k, 0, ws.data_ptr(), ctypes.c_int64(ws.numel()), _stream(x))
+            _native.call("m2f_conv_f32x3", x.data_ptr(), weight.data_ptr(), _native.ptr(bias), out.data_ptr(), N, Ci,
+                         Co, H, W, k, 0, ws.data_ptr(), ws.numel(), _native.stream(x))
         else:
             x, ctx.nhwc = _act16(x)
-            _native.call("m2f_conv_x3_io", x.data_ptr(), _DT[x.dtype], ctx.nhwc, weight.data_ptr(), _ptr(bias),
-                         out.data_ptr(), 0, 0, N, Ci, Co, H, W, k, 0, ws.data_ptr(), ctypes.c_int64(ws.numel()),
-                         _stream(x))
+            _native.call("m2f_conv_x3_io", x.data_ptr(), _native.dtype_code(x.dtype, "conv2d"), ctx.nhwc,
+                         weight.data_ptr(), _native.ptr(bias), out.data_ptr(), 0, 0, N, Ci, Co, H, W, k, 0,
+                         ws.data_ptr(), ws.numel(), _native.stream(x))
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         return out
@@ -90,19 +75,21 @@ class Conv2dX3(Function):
             if ctx.needs_input_grad[0]:
                 dx = (torch.empty(N, H, W, Ci, device=x.device, dtype=x.dtype).permute(0, 3, 1, 2) if ctx.nhwc
                       else torch.empty(N, Ci, H, W, device=x.device, dtype=x.dtype))
-                _native.call("m2f_conv_x3_io", g.data_ptr(), 0, 0, weight.data_ptr(), None, dx.data_ptr(), _DT[x.dtype],
-                             ctx.nhwc, N, Ci, Co, H, W, k, 1, ws.data_ptr(), ctypes.c_int64(ws.numel()), _stream(g))
+                _native.call("m2f_conv_x3_io", g.data_ptr(), 0, 0, weight.data_ptr(), None, dx.data_ptr(),
+                             _native.dtype_code(x.dtype, "conv2d"), ctx.nhwc, N, Ci, Co, H, W, k, 1, ws.data_ptr(),
+                             ws.numel(), _native.stream(g))
             if ctx.needs_input_grad[1] or want_b:
                 tck = torch.empty(k * k, Ci, Co, device=x.device, dtype=torch.float32)
                 db = torch.empty(Co, device=x.device, dtype=torch.float32) if want_b else None
-                _native.call("m2f_conv_x3_wgrad_io", g.data_ptr(), x.data_ptr(), _DT[x.dtype], ctx.nhwc, tck.data_ptr(),
-                             _ptr(db), N, Ci, Co, H, W, k, ws.data_ptr(), ctypes.c_int64(ws.numel()), _stream(g))
+                _native.call("m2f_conv_x3_wgrad_io", g.data_ptr(), x.data_ptr(), _native.dtype_code(x.dtype, "conv2d"),
+                             ctx.nhwc, tck.data_ptr(), _native.ptr(db), N, Ci, Co, H, W, k, ws.data_ptr(), ws.numel(),
+                             _native.stream(g))
                 dw = tck.permute(2, 1, 0).reshape(Co, Ci, k, k) if ctx.needs_input_grad[1] else None
             return dx, dw, db
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             _native.call("m2f_conv_f32x3", g.data_ptr(), weight.data_ptr(), None, dx.data_ptr(), N, Ci, Co, H, W, k, 1,
-                         ws.data_ptr(), ctypes.c_int64(ws.numel()), _stream(g))
+                         ws.data_ptr(), ws.numel(), _native.stream(g))
         if k == 3 and WGRAD3 == "tn" and ctx.needs_input_grad[1]:
             dw = _wgrad3_tn(g, x)
             db = g.sum((2, 3)).sum(0) if want_b else None   # two reductions with many outputs (graph-safe)
@@ -114,8 +101,8 @@ class Conv2dX3(Function):
         elif ctx.needs_input_grad[1] or want_b:
             tck = torch.empty(k * k, Ci, Co, device=x.device, dtype=torch.float32)
             db = torch.empty(Co, device=x.device, dtype=torch.float32) if want_b else None
-            _native.call("m2f_conv_f32x3_wgrad", g.data_ptr(), x.data_ptr(), tck.data_ptr(), _ptr(db), N, Ci, Co, H, W,
-                         k, ws.data_ptr(), ctypes.c_int64(ws.numel()), _stream(g))
+            _native.call("m2f_conv_f32x3_wgrad", g.data_ptr(), x.data_ptr(), tck.data_ptr(), _native.ptr(db), N, Ci, Co,
+                         H, W, k, ws.data_ptr(), ws.numel(), _native.stream(g))
             dw = tck.permute(2, 1, 0).reshape(Co, Ci, k, k) if ctx.needs_input_grad[1] else None
         return dx, dw, db
 
@@ -163,7 +150,7 @@ def _wgrad3_tn(g, x):
 
 def eligible(x, conv) -> bool:
     """Shapes and settings the x3 conv kernels cover (else F.conv2d): fp32 input, or a 16-bit one into a 1x1 conv."""
-    if not (x.is_cuda and x.dtype in _DT and conv.weight.dtype == torch.float32 and x.dim() == 4):
+    if not (x.is_cuda and x.dtype in _native.DTYPE_CODES and conv.weight.dtype == torch.float32 and x.dim() == 4):
         return False
     k = conv.weight.shape[-1]
     if x.dtype != torch.float32 and k != 1:
@@ -213,14 +200,14 @@ class Upsample2xAdd(Function):
             # the encoder's (N, HW, C) map read channel-contiguous and transposed in LDS: no transposing copy, and
             # the gradient comes back channels-last like the decoder's gradient of the same map (one fast sum)
             sN = src.stride(0) if N > 1 else h * w * C   # a size-1 batch dimension's stride is arbitrary
-            _native.call("m2f_upsample2x_add_fwd_nhwc_f32", src.data_ptr(), ctypes.c_int64(sN), lat.data_ptr(),
-                         out.data_ptr(), N, C, h, w, _stream(lat))
+            _native.call("m2f_upsample2x_add_fwd_nhwc_f32", src.data_ptr(), sN, lat.data_ptr(),
+                         out.data_ptr(), N, C, h, w, _native.stream(lat))
         else:
             # the strided read of a transposed (N, HW, C) view costs a cache line per lane and tap (2.6 ms at
             # bs16 128->256); one transposing copy first makes every tap read coalesced (1.0 ms with the copy)
             src = src.contiguous()
-            _native.call("m2f_upsample2x_add_fwd_f32", src.data_ptr(), *(ctypes.c_int64(s) for s in src.stride()),
-                         lat.data_ptr(), out.data_ptr(), N, C, h, w, _stream(lat))
+            _native.call("m2f_upsample2x_add_fwd_f32", src.data_ptr(), *src.stride(),
+                         lat.data_ptr(), out.data_ptr(), N, C, h, w, _native.stream(lat))
         ctx.src_shape = src.shape
         return out
 
@@ -232,10 +219,11 @@ class Upsample2xAdd(Function):
         if ctx.needs_input_grad[0]:
             if ctx.nhwc:
                 gsrc = torch.empty(N, h, w, C, device=g.device, dtype=torch.float32).permute(0, 3, 1, 2)
-                _native.call("m2f_upsample2x_bwd_nhwc_f32", g.data_ptr(), gsrc.data_ptr(), N, C, h, w, _stream(g))
+                _native.call("m2f_upsample2x_bwd_nhwc_f32", g.data_ptr(), gsrc.data_ptr(), N, C, h, w,
+                             _native.stream(g))
             else:
                 gsrc = torch.empty(N, C, h, w, device=g.device, dtype=torch.float32)
-                _native.call("m2f_upsample2x_bwd_f32", g.data_ptr(), gsrc.data_ptr(), N, C, h, w, _stream(g))
+                _native.call("m2f_upsample2x_bwd_f32", g.data_ptr(), gsrc.data_ptr(), N, C, h, w, _native.stream(g))
         return gsrc, (g if ctx.needs_input_grad[1] else None)
 
 
@@ -259,8 +247,7 @@ def upsample_add(src, lateral):
 
 
 def _transpose(src, in_bs, in_ld, dst, out_bs, out_ld, B, R, Q, device):
-    _native.call("m2f_transpose_f32", src, ctypes.c_int64(in_bs), ctypes.c_int64(in_ld), dst, ctypes.c_int64(out_bs),
-                 ctypes.c_int64(out_ld), B, R, Q, torch.cuda.current_stream(device).cuda_stream)
+    _native.call("m2f_transpose_f32", src, in_bs, in_ld, dst, out_bs, out_ld, B, R, Q, _native.stream(device))
 
 
 class FlattenLevels(Function):

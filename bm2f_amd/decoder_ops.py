@@ -24,19 +24,7 @@ from torch.autograd import Function
 from torch.nn import functional as F
 
 from . import _native
-
-_DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
-
-
-def _code(dtype):
-    try:
-        return _DTYPE_CODE[dtype]
-    except KeyError:
-        raise RuntimeError(f"bm2f_amd decoder ops: unsupported dtype {dtype}") from None
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
+from ._native import dtype_code
 
 
 def _require_device(*ts):
@@ -61,8 +49,8 @@ def attn_mask_bits(logits: torch.Tensor, size, row_fix: bool = True) -> torch.Te
     Hout, Wout = int(size[0]), int(size[1])
     nw = num_words(T * Hout * Wout)
     bits = torch.empty((B, Q, nw), dtype=torch.int32, device=logits.device)
-    _native.call("m2f_attn_mask_bits", logits.data_ptr(), _code(logits.dtype), B, Q, T, Hin, Win, Hout, Wout,
-                 1 if row_fix else 0, bits.data_ptr(), nw, _stream(logits))
+    _native.call("m2f_attn_mask_bits", logits.data_ptr(), dtype_code(logits.dtype, "attn_mask_bits"), B, Q, T, Hin, Win,
+                 Hout, Wout, 1 if row_fix else 0, bits.data_ptr(), nw, _native.stream(logits))
     return bits
 
 
@@ -75,11 +63,8 @@ def bits_to_bool(bits: torch.Tensor, hw: int, num_heads: int = 1) -> torch.Tenso
 
 
 def _plan(B, Lq, Lk, H):
-    cl, nc = ctypes.c_int(), ctypes.c_int()
-    fw, bw = ctypes.c_int64(), ctypes.c_int64()
-    _native.call("m2f_masked_attn_plan", B, Lq, Lk, H, ctypes.byref(cl), ctypes.byref(nc), ctypes.byref(fw),
-                 ctypes.byref(bw))
-    return cl.value, nc.value, fw.value, bw.value
+    """(chunk_len, num_chunks, forward workspace bytes, backward workspace bytes)."""
+    return _native.query("m2f_masked_attn_plan", B, Lq, Lk, H, outs="iill")
 
 
 def _rows(t: torch.Tensor):
@@ -112,9 +97,9 @@ class MaskedAttention(Function):
         out = torch.empty((B, Lq, C), dtype=q.dtype, device=q.device)
         lse = torch.empty((B, num_heads, Lq), dtype=torch.float32, device=q.device)
         ws = torch.empty((max(fwb, 4) // 4,), dtype=torch.float32, device=q.device)
-        _native.call("m2f_masked_attn_fwd", _code(q.dtype), q.data_ptr(), k.data_ptr(), v.data_ptr(), bits.data_ptr(),
-                     B, Lq, Lk, num_heads, 32, qs, ks, bits.shape[-1], ctypes.c_float(scale), out.data_ptr(),
-                     lse.data_ptr(), ws.data_ptr(), ctypes.c_int64(fwb), _stream(q))
+        _native.call("m2f_masked_attn_fwd", dtype_code(q.dtype, "masked attention"), q.data_ptr(), k.data_ptr(),
+                     v.data_ptr(), bits.data_ptr(), B, Lq, Lk, num_heads, 32, qs, ks, bits.shape[-1], scale,
+                     out.data_ptr(), lse.data_ptr(), ws.data_ptr(), fwb, _native.stream(q))
         ctx.save_for_backward(q, k, v, bits, out, lse)
         ctx.meta = (num_heads, scale, qs, ks)
         return out
@@ -131,10 +116,10 @@ class MaskedAttention(Function):
         dk = torch.empty((B, Lk, C), dtype=q.dtype, device=q.device)
         dv = torch.empty((B, Lk, C), dtype=q.dtype, device=q.device)
         ws = torch.empty((max(bwb, 4) // 4,), dtype=torch.float32, device=q.device)
-        _native.call("m2f_masked_attn_bwd", _code(q.dtype), q.data_ptr(), k.data_ptr(), v.data_ptr(), bits.data_ptr(),
-                     out.data_ptr(), grad_out.data_ptr(), lse.data_ptr(), B, Lq, Lk, num_heads, 32, qs, ks,
-                     bits.shape[-1], ctypes.c_float(scale), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
-                     ws.data_ptr(), ctypes.c_int64(bwb), _stream(q))
+        _native.call("m2f_masked_attn_bwd", dtype_code(q.dtype, "masked attention"), q.data_ptr(), k.data_ptr(),
+                     v.data_ptr(), bits.data_ptr(), out.data_ptr(), grad_out.data_ptr(), lse.data_ptr(), B, Lq, Lk,
+                     num_heads, 32, qs, ks, bits.shape[-1], scale, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+                     ws.data_ptr(), bwb, _native.stream(q))
         return dq, dk, dv, None, None, None
 
 
@@ -240,12 +225,12 @@ def mask_heads_bwd_embed(g, f):
     """d embed = g f^T: g (B, Q, N), f (B, 256, N) in bf16 / fp16 -> (B, Q, 256) in that dtype."""
     B, C, N = f.shape
     Q = g.shape[1]
-    wb = ctypes.c_int64()
-    _native.call("m2f_mask_heads_bwd_workspace", B, Q, ctypes.c_int64(N), ctypes.byref(wb))
-    ws = torch.empty((max(wb.value, 4) // 4,), dtype=torch.float32, device=g.device)
+    wb = _native.query("m2f_mask_heads_bwd_workspace", B, Q, N)
+    ws = torch.empty((max(wb, 4) // 4,), dtype=torch.float32, device=g.device)
     de = torch.empty((B, Q, C), dtype=g.dtype, device=g.device)
-    _native.call("m2f_mask_heads_bwd_embed", _code(g.dtype), g.data_ptr(), f.data_ptr(), B, Q, C, ctypes.c_int64(N),
-                 de.data_ptr(), ws.data_ptr(), ctypes.c_int64(wb.value), _stream(g))
+    # n stays a ctypes object here and in mask_heads_bwd_feats: bench.py --full reads it as ``.value`` (its ENTRIES)
+    _native.call("m2f_mask_heads_bwd_embed", dtype_code(g.dtype, "mask_heads_bwd_embed"), g.data_ptr(), f.data_ptr(), B,
+                 Q, C, ctypes.c_int64(N), de.data_ptr(), ws.data_ptr(), wb, _native.stream(g))
     return de
 
 
@@ -262,8 +247,9 @@ def mask_heads_bwd_feats(es, gs, out_dtype):
     et = et.view(B, H * QP // 16, 2, 8, C // 32, 32).permute(0, 4, 1, 2, 5, 3).contiguous()
     ptrs = (ctypes.c_void_p * H)(*[g.data_ptr() for g in gs])
     df = torch.empty((B, C, N), dtype=out_dtype, device=gs[0].device)
-    _native.call("m2f_mask_heads_bwd_feats", _code(gs[0].dtype), ctypes.cast(ptrs, ctypes.c_void_p), H, et.data_ptr(),
-                 B, Q, QP, C, ctypes.c_int64(N), _code(out_dtype), df.data_ptr(), _stream(gs[0]))
+    what = "mask_heads_bwd_feats"
+    _native.call("m2f_mask_heads_bwd_feats", dtype_code(gs[0].dtype, what), ptrs, H, et.data_ptr(), B, Q, QP, C,
+                 ctypes.c_int64(N), dtype_code(out_dtype, what), df.data_ptr(), _native.stream(gs[0]))
     return df
 
 
@@ -324,9 +310,9 @@ class _FoldedMaskHeads(Function):
             h = w = nw = 0
             bits = torch.empty((0,), dtype=torch.int32, device=f.device)
             bp = None
-        st = _stream(f)
-        _native.call("m2f_mask_heads_fwd", _code(f.dtype), e.data_ptr(), f.data_ptr(), B, Q, C, T, H, W, h, w,
-                     out.data_ptr(), bp, nw, st)
+        st = _native.stream(f)
+        _native.call("m2f_mask_heads_fwd", dtype_code(f.dtype, "mask_heads"), e.data_ptr(), f.data_ptr(), B, Q, C, T, H,
+                     W, h, w, out.data_ptr(), bp, nw, st)
         if size is not None:
             _native.call("m2f_mask_row_fix", bp, B * Q, nw, keys, st)
         ctx.mark_non_differentiable(bits)
@@ -415,10 +401,9 @@ def colsum_f32(g2):
     out = torch.empty(C, dtype=torch.float32, device=g2.device)
     if R == 0:
         return out.zero_()
-    wf = ctypes.c_int64(0)
-    _native.call("m2f_colsum_workspace", R, C, ctypes.byref(wf))
-    ws = torch.empty(wf.value, dtype=torch.float32, device=g2.device)
-    _native.call("m2f_colsum", _code(g2.dtype), g2.data_ptr(), R, C, ws.data_ptr(), wf, out.data_ptr(), _stream(g2))
+    ws = _native.workspace("m2f_colsum_workspace", R, C, device=g2.device, dtype=torch.float32)
+    _native.call("m2f_colsum", dtype_code(g2.dtype, "colsum_f32"), g2.data_ptr(), R, C, ws.data_ptr(), ws.numel(),
+                 out.data_ptr(), _native.stream(g2))
     return out
 
 
@@ -588,7 +573,8 @@ def sum_to_f32(terms):
         return out
     out = torch.empty(t0.shape, dtype=torch.float32, device=t0.device)
     ptrs = (ctypes.c_void_p * len(terms))(*[t.data_ptr() for t in terms])
-    _native.call("m2f_sum_to_f32", ptrs, len(terms), t0.numel(), _code(t0.dtype), out.data_ptr(), _stream(t0))
+    _native.call("m2f_sum_to_f32", ptrs, len(terms), t0.numel(), dtype_code(t0.dtype, "sum_to_f32"), out.data_ptr(),
+                 _native.stream(t0))
     return out
 
 

@@ -28,21 +28,9 @@ from torch import nn
 from . import _native
 from .rle import _BYTES, _encode_device, rle_encode
 
-_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 _MAX_Q = 256
 _MAX_K = 256
 _INSTANCE_TILE = 1024
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _code(t):
-    try:
-        return _CODES[t.dtype]
-    except KeyError:
-        raise RuntimeError(f"bm2f_amd inference: unsupported mask dtype {t.dtype}") from None
 
 
 def _pair(s):
@@ -162,8 +150,9 @@ def _semantic_hip(mask_cls, mask_pred, padded_size, geo, labels=False):
     else:
         out = torch.empty((B, K, Ho, Wo), dtype=torch.float32, device=masks.device)
         sem_ptr, lab_ptr = out.data_ptr(), None
-    _native.call("m2f_infer_semantic", masks.data_ptr(), _code(masks), probs.data_ptr(), sizes.data_ptr(), B, Q, K, h,
-                 w, Hp, Wp, Ho, Wo, sem_ptr, lab_ptr, _stream(masks))
+    _native.call("m2f_infer_semantic", masks.data_ptr(), _native.dtype_code(masks.dtype, "inference masks"),
+                 probs.data_ptr(), sizes.data_ptr(), B, Q, K, h, w, Hp, Wp, Ho, Wo, sem_ptr, lab_ptr,
+                 _native.stream(masks))
     return [out[b, ..., :g[2], :g[3]] for b, g in enumerate(geo)]
 
 
@@ -179,9 +168,9 @@ def _panoptic_pass_hip(mask_cls, mask_pred, padded_size, geo, num_classes, objec
     winner = torch.empty((B, Ho, Wo), dtype=torch.int16, device=masks.device)
     inside = torch.empty((B, Ho, Wo), dtype=torch.uint8, device=masks.device)
     counters = torch.empty((B, Q, 3), dtype=torch.int32, device=masks.device)
-    _native.call("m2f_infer_panoptic_pass", masks.data_ptr(), _code(masks), keep_idx.data_ptr(), kscore.data_ptr(),
-                 n_keep32.data_ptr(), sizes.data_ptr(), B, Q, h, w, Hp, Wp, Ho, Wo, winner.data_ptr(),
-                 inside.data_ptr(), counters.data_ptr(), _stream(masks))
+    _native.call("m2f_infer_panoptic_pass", masks.data_ptr(), _native.dtype_code(masks.dtype, "inference masks"),
+                 keep_idx.data_ptr(), kscore.data_ptr(), n_keep32.data_ptr(), sizes.data_ptr(), B, Q, h, w, Hp, Wp, Ho,
+                 Wo, winner.data_ptr(), inside.data_ptr(), counters.data_ptr(), _native.stream(masks))
     # the one device-to-host copy of the head: counters, classes and counts of the whole batch
     packed = torch.cat([counters.flatten(1), kclass.to(torch.int32), n_keep32[:, None]], dim=1).cpu()
     return winner, inside, packed
@@ -249,9 +238,9 @@ def _instance_hip(mask_cls, mask_pred, padded_size, geo, num_classes, topk, thin
     binary = torch.empty((B, S, Ho, Wo), dtype=torch.uint8, device=masks.device)
     partials = torch.empty((B, S, tiles, 2), dtype=torch.float32, device=masks.device)
     sums = torch.empty((B, S, 2), dtype=torch.float32, device=masks.device)
-    _native.call("m2f_infer_instance", masks.data_ptr(), _code(masks), sel.data_ptr(), n_sel.data_ptr(),
-                 sizes.data_ptr(), B, Q, S, h, w, Hp, Wp, Ho, Wo, tiles, binary.data_ptr(), partials.data_ptr(),
-                 sums.data_ptr(), _stream(masks))
+    _native.call("m2f_infer_instance", masks.data_ptr(), _native.dtype_code(masks.dtype, "inference masks"),
+                 sel.data_ptr(), n_sel.data_ptr(), sizes.data_ptr(), B, Q, S, h, w, Hp, Wp, Ho, Wo, tiles,
+                 binary.data_ptr(), partials.data_ptr(), sums.data_ptr(), _native.stream(masks))
     results = []
     for b, g in enumerate(geo):
         slot, sc, lab = rank[b].gather(0, qidx[b]), scores[b], labels[b]

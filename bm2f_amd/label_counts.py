@@ -25,13 +25,11 @@ that is not a fallback: on a HIP tensor a kernel error raises ``NativeError``.
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _native
-from .mask_iou import _ptr, _upload
+from .mask_iou import _upload
 
 _A_DTYPES = (np.uint8, np.int16, np.int32)
 _B_DTYPES = (np.uint8, np.int16, np.int32, np.int64)
@@ -45,9 +43,7 @@ def geometry():
     workgroup, the counters the LDS path can hold and the longest id list."""
     global _geometry
     if _geometry is None:
-        v = [ctypes.c_int() for _ in range(4)]
-        _native.call("m2f_label_counts_geometry", *(ctypes.byref(x) for x in v))
-        _geometry = tuple(x.value for x in v)
+        _geometry = _native.query("m2f_label_counts_geometry", outs="iiii")
     return _geometry
 
 
@@ -239,11 +235,11 @@ def _counts_device(plan):
         dev = _upload({"images": images, "ids": flat_ids, "blocks": blocks}, device)             # one copy
         out = torch.zeros(plan["out_len"] + G, dtype=torch.int64, device=device)
         ign = plan["ignore"]
-        _native.call("m2f_label_pair_counts_ragged", a_base or None, plan["a_dtype"].itemsize, a_elems,
-                     b_base or None, plan["b_dtype"].itemsize, b_elems, dev["images"].data_ptr(), G, _ptr(dev["ids"]),
-                     flat_ids.size, _ptr(dev["blocks"]), blocks.shape[0], int(ign is not None), ign or 0, max_bins,
-                     _PATHS[plan["path"]], out.data_ptr(), plan["out_len"], out.data_ptr() + 8 * plan["out_len"],
-                     torch.cuda.current_stream(device).cuda_stream)
+        _native.call("m2f_label_pair_counts_ragged", a_base or None, plan["a_dtype"].itemsize, a_elems, b_base or None,
+                     plan["b_dtype"].itemsize, b_elems, dev["images"].data_ptr(), G, _native.ptr_or_null(dev["ids"]),
+                     flat_ids.size, _native.ptr_or_null(dev["blocks"]), blocks.shape[0], int(ign is not None), ign or 0,
+                     max_bins, _PATHS[plan["path"]], out.data_ptr(), plan["out_len"],
+                     out.data_ptr() + 8 * plan["out_len"], _native.stream(device))
         host = out.cpu().numpy()                                                                  # the one copy
     del keep_a, keep_b
     return host[:plan["out_len"]], host[plan["out_len"]:]

@@ -21,8 +21,6 @@ every fused-epilogue product and the 256-wide products run on libbm2f.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -43,14 +41,6 @@ def _engine(engine):
     return e
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _c64(v):
-    return ctypes.c_int64(int(v))
-
-
 def gemm_nt(a, b, bias=None, relu=False, mask=None, out=None, engine=None, b_kn=False, add=()):
     """C = a @ b.T (+ bias) (ReLU | * (mask > 0)) (+ add[0] (+ add[1])); a (M, K), b (N, K) fp32 row-major
     (unit column stride).  With ``b_kn`` b is (K, N) and C = a @ b (x3 engine: read in place; exact engine:
@@ -60,32 +50,29 @@ def gemm_nt(a, b, bias=None, relu=False, mask=None, out=None, engine=None, b_kn=
     N = b.shape[1] if b_kn else b.shape[0]
     if out is None:
         out = torch.empty(M, N, device=a.device, dtype=torch.float32)
-    msk = (mask.data_ptr() if mask is not None else None, _c64(mask.stride(0) if mask is not None else 0))
+    msk = (_native.ptr(mask), mask.stride(0) if mask is not None else 0)
     add = [d for d in add if d is not None]
     if _engine(engine) == "x3":
-        wsb = ctypes.c_int64(0)
-        _native.call("m2f_gemm_f32x3_nt_workspace", N, K, ctypes.byref(wsb))
-        ws = torch.empty(max(wsb.value, 16), device=a.device, dtype=torch.uint8)
+        ws = _native.workspace("m2f_gemm_f32x3_nt_workspace", N, K, device=a.device, floor=16)
         if add:
             if len(add) > 2 or any(d.shape != (M, N) or d.stride() != add[0].stride() or d.stride(1) != 1
                                    for d in add):
                 raise RuntimeError("gemm_nt: addends must be (M, N) row-major tensors with one row stride")
-            _native.call("m2f_gemm_f32x3_nt_add", a.data_ptr(), _c64(a.stride(0)), b.data_ptr(), _c64(b.stride(0)),
-                         1 if b_kn else 0, bias.data_ptr() if bias is not None else None, 1 if relu else 0, *msk,
-                         add[0].data_ptr(), add[1].data_ptr() if len(add) > 1 else None, _c64(add[0].stride(0)),
-                         out.data_ptr(), _c64(out.stride(0)), M, N, K, ws.data_ptr(), _c64(ws.numel()), _stream(a))
+            _native.call("m2f_gemm_f32x3_nt_add", a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0),
+                         1 if b_kn else 0, _native.ptr(bias), 1 if relu else 0, *msk,
+                         add[0].data_ptr(), add[1].data_ptr() if len(add) > 1 else None, add[0].stride(0),
+                         out.data_ptr(), out.stride(0), M, N, K, ws.data_ptr(), ws.numel(), _native.stream(a))
             return out
-        _native.call("m2f_gemm_f32x3_nt", a.data_ptr(), _c64(a.stride(0)), b.data_ptr(), _c64(b.stride(0)),
-                     1 if b_kn else 0, bias.data_ptr() if bias is not None else None, 1 if relu else 0, *msk,
-                     out.data_ptr(), _c64(out.stride(0)), M, N, K, ws.data_ptr(), _c64(ws.numel()), _stream(a))
+        _native.call("m2f_gemm_f32x3_nt", a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0),
+                     1 if b_kn else 0, _native.ptr(bias), 1 if relu else 0, *msk,
+                     out.data_ptr(), out.stride(0), M, N, K, ws.data_ptr(), ws.numel(), _native.stream(a))
         return out
     if add:
         raise RuntimeError("gemm_nt: addends need the x3 engine")
     if b_kn:
         b = b.t().contiguous()
-    _native.call("m2f_gemm_f32_nt", a.data_ptr(), _c64(a.stride(0)), b.data_ptr(), _c64(b.stride(0)),
-                 bias.data_ptr() if bias is not None else None, 1 if relu else 0, *msk,
-                 out.data_ptr(), _c64(out.stride(0)), M, N, K, _stream(a))
+    _native.call("m2f_gemm_f32_nt", a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), _native.ptr(bias),
+                 1 if relu else 0, *msk, out.data_ptr(), out.stride(0), M, N, K, _native.stream(a))
     return out
 
 
@@ -94,12 +81,10 @@ def gemm_nt_rowadd(a, b, r, period):
     M, K = a.shape
     N = b.shape[0]
     out = torch.empty(M, N, device=a.device, dtype=torch.float32)
-    wsb = ctypes.c_int64(0)
-    _native.call("m2f_gemm_f32x3_nt_workspace", N, K, ctypes.byref(wsb))
-    ws = torch.empty(max(wsb.value, 16), device=a.device, dtype=torch.uint8)
-    _native.call("m2f_gemm_f32x3_nt_rowadd", a.data_ptr(), _c64(a.stride(0)), b.data_ptr(), _c64(b.stride(0)), 0,
-                 r.data_ptr(), _c64(r.stride(0)), period, out.data_ptr(), _c64(out.stride(0)), M, N, K, ws.data_ptr(),
-                 _c64(ws.numel()), _stream(a))
+    ws = _native.workspace("m2f_gemm_f32x3_nt_workspace", N, K, device=a.device, floor=16)
+    _native.call("m2f_gemm_f32x3_nt_rowadd", a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), 0,
+                 r.data_ptr(), r.stride(0), period, out.data_ptr(), out.stride(0), M, N, K, ws.data_ptr(),
+                 ws.numel(), _native.stream(a))
     return out
 
 
@@ -110,14 +95,10 @@ def gemm_nt_bits(a, b, bias=None, bits_out=None, bits_in=None, b_kn=False):
     N = b.shape[1] if b_kn else b.shape[0]
     out = torch.empty(M, N, device=a.device, dtype=torch.float32)
     bits = bits_out if bits_out is not None else bits_in
-    wsb = ctypes.c_int64(0)
-    _native.call("m2f_gemm_f32x3_nt_workspace", N, K, ctypes.byref(wsb))
-    ws = torch.empty(max(wsb.value, 16), device=a.device, dtype=torch.uint8)
-    _native.call("m2f_gemm_f32x3_nt_bits", a.data_ptr(), _c64(a.stride(0)), b.data_ptr(), _c64(b.stride(0)),
-                 1 if b_kn else 0, bias.data_ptr() if bias is not None else None, 1 if bits_out is not None else 0,
-                 bits_out.data_ptr() if bits_out is not None else None,
-                 bits_in.data_ptr() if bits_in is not None else None, _c64(bits.stride(0)),
-                 out.data_ptr(), _c64(out.stride(0)), M, N, K, ws.data_ptr(), _c64(ws.numel()), _stream(a))
+    ws = _native.workspace("m2f_gemm_f32x3_nt_workspace", N, K, device=a.device, floor=16)
+    _native.call("m2f_gemm_f32x3_nt_bits", a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), 1 if b_kn else 0,
+                 _native.ptr(bias), 1 if bits_out is not None else 0, _native.ptr(bits_out), _native.ptr(bits_in),
+                 bits.stride(0), out.data_ptr(), out.stride(0), M, N, K, ws.data_ptr(), ws.numel(), _native.stream(a))
     return out
 
 
@@ -144,12 +125,9 @@ def gemm_tn(a, b, colsum=False, engine=None):
     out = torch.empty(N1, N2, device=a.device, dtype=torch.float32)
     cs = torch.empty(N1, device=a.device, dtype=torch.float32) if colsum else None
     fn = "m2f_gemm_f32x3_tn" if _engine(engine) == "x3" else "m2f_gemm_f32_tn"
-    wsb = ctypes.c_int64(0)
-    _native.call(fn + "_workspace", M, N1, N2, ctypes.byref(wsb))
-    ws = torch.empty(max(wsb.value, 4), device=a.device, dtype=torch.uint8)
-    _native.call(fn, a.data_ptr(), _c64(a.stride(0)), b.data_ptr(), _c64(b.stride(0)),
-                 out.data_ptr(), _c64(N2), cs.data_ptr() if cs is not None else None, M, N1, N2, ws.data_ptr(),
-                 _c64(ws.numel()), _stream(a))
+    ws = _native.workspace(fn + "_workspace", M, N1, N2, device=a.device, floor=4)
+    _native.call(fn, a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), out.data_ptr(), N2, _native.ptr(cs),
+                 M, N1, N2, ws.data_ptr(), ws.numel(), _native.stream(a))
     return out, cs
 
 

@@ -43,8 +43,6 @@ scipy).  That is not a fall-back: on a HIP tensor a kernel error raises.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 import torch.nn.functional as F
 from torch.autograd import Function
@@ -52,8 +50,6 @@ from torch.autograd import Function
 from . import _native
 from . import weaksup as ws
 from .set_criterion import _class_cost, _Matcher, _SetCriterion, _Targets
-
-_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 
 def _rand_source(kind, shape, device):
@@ -68,7 +64,7 @@ def point_sample(x, u):
 
 def _logit_tensor(masks):
     """The masks in a dtype the kernels read (fp32 / fp16 / bf16), contiguous."""
-    if masks.dtype not in _DTYPES:
+    if masks.dtype not in _native.DTYPE_CODES:
         masks = masks.float()
     return masks.contiguous()
 
@@ -137,14 +133,12 @@ def match_cost(masks, coords, tgt_table, tgt_code, Gm, cost_class=None, w_class=
         cc = cost_class.to(torch.float32).contiguous()
         if cc.shape != (B, Q, Gm):
             raise ValueError("cost_class must be (B, Q, Gm)")
-    n = ctypes.c_int64()
-    _native.call("m2f_point_match_workspace", B, T, Q, Gm, K, ctypes.byref(n))
-    work = torch.empty(max(n.value, 1), dtype=torch.float32, device=x.device)
+    n = _native.query("m2f_point_match_workspace", B, T, Q, Gm, K)
+    work = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
     cost = torch.empty((B, Q, Gm), dtype=torch.float32, device=x.device)
-    _native.call("m2f_point_match_cost", x.data_ptr(), _DTYPES[x.dtype], B, Q, T, H, W, c.data_ptr(), K,
-                 tgt_table.contiguous().data_ptr(), tgt_code, Gm, ws._ptr(cc), ctypes.c_float(w_class),
-                 ctypes.c_float(w_mask), ctypes.c_float(w_dice), work.data_ptr(), ctypes.c_int64(n.value),
-                 cost.data_ptr(), ws._stream(x))
+    _native.call("m2f_point_match_cost", x.data_ptr(), _native.dtype_code(x.dtype, "mask criterion"), B, Q, T, H, W,
+                 c.data_ptr(), K, tgt_table.contiguous().data_ptr(), tgt_code, Gm, _native.ptr(cc), w_class, w_mask,
+                 w_dice, work.data_ptr(), n, cost.data_ptr(), _native.stream(x))
     return cost
 
 
@@ -157,8 +151,9 @@ def point_uncertainty(masks, plane, coords):
     R, P = coords.shape[:2]
     c = coords.to(torch.float32).contiguous()
     out = torch.empty((R, P), dtype=torch.float32, device=x.device)
-    _native.call("m2f_point_uncertainty", x.data_ptr(), _DTYPES[x.dtype], ctypes.c_int64(x.numel() // (H * W)), H, W,
-                 plane.contiguous().data_ptr(), R, c.data_ptr(), P, out.data_ptr(), ws._stream(x))
+    _native.call("m2f_point_uncertainty", x.data_ptr(), _native.dtype_code(x.dtype, "mask criterion"),
+                 x.numel() // (H * W), H, W, plane.contiguous().data_ptr(), R, c.data_ptr(), P, out.data_ptr(),
+                 _native.stream(x))
     return out
 
 
@@ -175,9 +170,9 @@ class PointLossSums(Function):
         chunks = _native.load().m2f_point_loss_chunks(K)
         part = torch.empty((R, max(chunks, 1), 4), dtype=torch.float32, device=masks.device)
         n_planes = masks.numel() // (H * W)
-        _native.call("m2f_point_loss_fwd", masks.data_ptr(), _DTYPES[masks.dtype], ctypes.c_int64(n_planes), H, W,
-                     plane.data_ptr(), R, coords.data_ptr(), K, tgt_rows.data_ptr(), tgt_code, part.data_ptr(),
-                     ws._stream(masks))
+        _native.call("m2f_point_loss_fwd", masks.data_ptr(), _native.dtype_code(masks.dtype, "mask criterion"),
+                     n_planes, H, W, plane.data_ptr(), R, coords.data_ptr(), K, tgt_rows.data_ptr(), tgt_code,
+                     part.data_ptr(), _native.stream(masks))
         ctx.save_for_backward(masks, plane, coords, tgt_rows)
         ctx.tgt_code = tgt_code
         ctx.keep = keep                      # the target tensors the pointer table refers to
@@ -193,9 +188,9 @@ class PointLossSums(Function):
         R, K = coords.shape[:2]
         g = torch.stack([g_bce, g_inter, g_sig], 1).to(torch.float32).contiguous()
         grad = torch.zeros(masks.shape, dtype=torch.float32, device=masks.device)
-        _native.call("m2f_point_loss_bwd", masks.data_ptr(), _DTYPES[masks.dtype], ctypes.c_int64(grad.numel() // (H * W)),
-                     H, W, plane.data_ptr(), R, coords.data_ptr(), K, tgt_rows.data_ptr(), ctx.tgt_code, g.data_ptr(),
-                     grad.data_ptr(), ws._stream(masks))
+        _native.call("m2f_point_loss_bwd", masks.data_ptr(), _native.dtype_code(masks.dtype, "mask criterion"),
+                     grad.numel() // (H * W), H, W, plane.data_ptr(), R, coords.data_ptr(), K, tgt_rows.data_ptr(),
+                     ctx.tgt_code, g.data_ptr(), grad.data_ptr(), _native.stream(masks))
         return grad.to(masks.dtype), None, None, None, None, None
 
 

@@ -21,8 +21,6 @@ error raises ``NativeError``.
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
@@ -34,9 +32,7 @@ _POP8 = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(1).as
 
 def pair_tiles():
     """(TA, TB, chunk_words) of ``m2f_bits_pair_counts``: the instance tile and the word positions of a workgroup."""
-    ta, tb, cw = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _native.call("m2f_bits_pair_tiles", ctypes.byref(ta), ctypes.byref(tb), ctypes.byref(cw))
-    return ta.value, tb.value, cw.value
+    return _native.query("m2f_bits_pair_tiles", outs="iii")
 
 
 # -------------------------------------------------------------------------------------------------------------------
@@ -176,11 +172,11 @@ def rle_to_bits(rles, device=None, size=None) -> torch.Tensor:
     dev = _upload({"offsets": offsets, "positions": positions}, device)      # one copy
     off, pos = dev["offsets"], dev["positions"]
     out = torch.empty((M, H, (W + 31) // 32), dtype=torch.int32, device=device)
-    st = torch.cuda.current_stream(device).cuda_stream
+    st = _native.stream(device)
     with torch.cuda.device(device):
         for m0 in range(0, M, _MAX_MASKS):
             m1 = min(M, m0 + _MAX_MASKS)
-            _native.call("m2f_rle_decode_bits", pos.data_ptr() if pos.numel() else None, pos.numel(),
+            _native.call("m2f_rle_decode_bits", _native.ptr_or_null(pos), pos.numel(),
                          off[m0:].data_ptr(), m1 - m0, H, W, out[m0:].data_ptr(), st)
     return out
 
@@ -243,15 +239,13 @@ def mask_pair_counts(a_bits, b_bits, width):
     dev = a_bits.device
     a, sa = _instances(a_bits.detach(), T * H * words)
     b, sb = _instances(b_bits.detach(), T * H * words)
-    nbytes = ctypes.c_int64()
-    _native.call("m2f_bits_pair_workspace", Da, Db, T, H, W, ctypes.byref(nbytes))
-    work = torch.empty((nbytes.value + 3) // 4, dtype=torch.int32, device=dev)
+    # the query reports a multiple of 4 bytes
+    work = _native.workspace("m2f_bits_pair_workspace", Da, Db, T, H, W, device=dev, dtype=torch.int32, unit=4)
     out = torch.empty(Da * Db + (Da + Db) * T, dtype=torch.int64, device=dev)
     n0, n1 = Da * Db, Da * Db + Da * T
     with torch.cuda.device(dev):
         _native.call("m2f_bits_pair_counts", a.data_ptr(), Da, sa, b.data_ptr(), Db, sb, T, H, W, out.data_ptr(),
-                     out[n0:].data_ptr(), out[n1:].data_ptr(), work.data_ptr(), work.numel() * 4,
-                     torch.cuda.current_stream(dev).cuda_stream)
+                     out[n0:].data_ptr(), out[n1:].data_ptr(), work.data_ptr(), work.numel() * 4, _native.stream(dev))
     host = out.cpu().numpy()                                          # the one copy
     return host[:n0].reshape(Da, Db), host[n0:n1].reshape(Da, T), host[n1:].reshape(Db, T)
 
@@ -371,17 +365,13 @@ def _upload(tables, device):
     return out
 
 
-def _ptr(t):
-    return t.data_ptr() if t.numel() else None
-
-
 def _launch_decode(dev_tables, num_masks, words, device):
     t = dev_tables
     with torch.cuda.device(device):
-        _native.call("m2f_rle_decode_bits_ragged", _ptr(t["positions"]), t["positions"].numel(),
+        _native.call("m2f_rle_decode_bits_ragged", _native.ptr_or_null(t["positions"]), t["positions"].numel(),
                      t["offsets"].data_ptr(), num_masks, t["sizes"].data_ptr(), t["out_offsets"].data_ptr(),
-                     _ptr(t["blocks"]), t["blocks"].numel() // 2, _ptr(words), words.numel(),
-                     torch.cuda.current_stream(device).cuda_stream)
+                     _native.ptr_or_null(t["blocks"]), t["blocks"].numel() // 2, _native.ptr_or_null(words),
+                     words.numel(), _native.stream(device))
 
 
 def rle_to_bits_ragged(rles, device=None, sizes=None):
@@ -483,16 +473,15 @@ def _launch_pairs(words, desc, dev_tables, num_tiles, device):
     """-> the device int64 output [inter | area_a | area_b]."""
     n_inter = int((desc[:, 2] * desc[:, 3]).sum())
     n_a, n_b = int(desc[:, 2].sum()), int(desc[:, 3].sum())
-    nbytes = ctypes.c_int64()
-    _native.call("m2f_bits_pair_ragged_workspace", num_tiles, ctypes.byref(nbytes))
-    work = torch.empty(max(nbytes.value // 4, 1), dtype=torch.int32, device=device)
+    work = _native.workspace("m2f_bits_pair_ragged_workspace", num_tiles, device=device, dtype=torch.int32, floor=4,
+                             unit=4)
     out = torch.empty(max(n_inter + n_a + n_b, 1), dtype=torch.int64, device=device)
     t = dev_tables
     with torch.cuda.device(device):
-        _native.call("m2f_bits_pair_counts_ragged", _ptr(words), words.numel(), t["groups"].data_ptr(), desc.shape[0],
-                     _ptr(t["a_off"]), n_a, _ptr(t["b_off"]), n_b, _ptr(t["tiles"]), num_tiles, n_inter,
-                     out.data_ptr(), out.data_ptr() + 8 * n_inter, out.data_ptr() + 8 * (n_inter + n_a),
-                     work.data_ptr(), work.numel() * 4, torch.cuda.current_stream(device).cuda_stream)
+        _native.call("m2f_bits_pair_counts_ragged", _native.ptr_or_null(words), words.numel(), t["groups"].data_ptr(),
+                     desc.shape[0], _native.ptr_or_null(t["a_off"]), n_a, _native.ptr_or_null(t["b_off"]), n_b,
+                     _native.ptr_or_null(t["tiles"]), num_tiles, n_inter, out.data_ptr(), out.data_ptr() + 8 * n_inter,
+                     out.data_ptr() + 8 * (n_inter + n_a), work.data_ptr(), work.numel() * 4, _native.stream(device))
     return out[:n_inter + n_a + n_b]
 
 

@@ -121,15 +121,8 @@ def _check(t: torch.Tensor, name: str) -> None:
         raise RuntimeError(f"{name} must be a CUDA tensor")
 
 
-def _ptr(t: torch.Tensor) -> int:
-    return t.data_ptr()
-
-
-def _stream(device: torch.device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
-
-
 def _host_shape_buffer(shapes):
+    """The int64 host array the entry points take as ``host_spatial_shapes`` (None -> NULL)."""
     if shapes is None:
         return None
     flat = [v for hw in shapes for v in hw]
@@ -173,9 +166,9 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     # an untagged device spatial_shapes is read back once and tagged (the reference's own MSDeformAttnFunction
     # saves this tensor object for its backward, where the tag then selects the tiled kernel)
     host = _host_shape_buffer(_host_shapes(spatial_shapes, level_start_index, derive=True))
-    _native.call(f"m2f_msda_fwd_{sfx}", _ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
-                 _ptr(sampling_loc), _ptr(attn_weight), N, S, M, D, L, Lq, P, int(im2col_step),
-                 ctypes.cast(host, ctypes.c_void_p) if host is not None else None, _ptr(out), _stream(value.device))
+    _native.call(f"m2f_msda_fwd_{sfx}", value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+                 sampling_loc.data_ptr(), attn_weight.data_ptr(), N, S, M, D, L, Lq, P, int(im2col_step), host,
+                 out.data_ptr(), _native.stream(value))
     return out
 
 
@@ -193,10 +186,10 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
     grad_loc = torch.empty_like(sampling_loc)
     grad_attn = torch.empty_like(attn_weight)
     host = _host_shape_buffer(_host_shapes(spatial_shapes, level_start_index, derive=True))
-    _native.call(f"m2f_msda_bwd_{sfx}", _ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
-                 _ptr(sampling_loc), _ptr(attn_weight), _ptr(grad_output), N, S, M, D, L, Lq, P, int(im2col_step),
-                 ctypes.cast(host, ctypes.c_void_p) if host is not None else None,
-                 _ptr(grad_value), _ptr(grad_loc), _ptr(grad_attn), _stream(value.device))
+    _native.call(f"m2f_msda_bwd_{sfx}", value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+                 sampling_loc.data_ptr(), attn_weight.data_ptr(), grad_output.data_ptr(), N, S, M, D, L, Lq, P,
+                 int(im2col_step), host, grad_value.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr(),
+                 _native.stream(value))
     return [grad_value, grad_loc, grad_attn]
 
 
@@ -250,9 +243,9 @@ class MSDeformAttnFusedFunction(Function):
             proj = proj.contiguous()
         hs = _host_shape_buffer(host_shapes)
         out = torch.empty((N, S, M * D), dtype=value.dtype, device=value.device)
-        _native.call("m2f_msda_fused_fwd_hm_f32" if head_major else "m2f_msda_fused_fwd_f32", _ptr(value), _ptr(proj),
-                     proj.stride(1), _ptr(ref), ref.stride(0), ctypes.cast(hs, ctypes.c_void_p), N, S, M, D, L, S,
-                     n_points, _ptr(out), _stream(value.device))
+        _native.call("m2f_msda_fused_fwd_hm_f32" if head_major else "m2f_msda_fused_fwd_f32", value.data_ptr(),
+                     proj.data_ptr(), proj.stride(1), ref.data_ptr(), ref.stride(0), hs, N, S, M, D, L, S, n_points,
+                     out.data_ptr(), _native.stream(value))
         ctx.save_for_backward(value, proj, ref)
         ctx.meta = (tuple(host_shapes), n_points, bool(head_major))
         return out
@@ -273,14 +266,12 @@ class MSDeformAttnFusedFunction(Function):
         if torch.are_deterministic_algorithms_enabled() and _native.get_option("msda_bwd_det") < 0:
             with _native.options(msda_bwd_det=1):
                 return MSDeformAttnFusedFunction.backward(ctx, grad_out)
-        ws_bytes = ctypes.c_int64(0)
-        _native.call("m2f_msda_fused_bwd_workspace", ctypes.cast(hs, ctypes.c_void_p), N, S, M, D, L, n_points,
-                     ctypes.byref(ws_bytes))
-        ws = torch.empty(ws_bytes.value, dtype=torch.uint8, device=value.device) if ws_bytes.value else None
-        _native.call("m2f_msda_fused_bwd_hm_f32" if head_major else "m2f_msda_fused_bwd_f32", _ptr(value),
-                     _ptr(proj), proj.stride(1), _ptr(ref), ref.stride(0), ctypes.cast(hs, ctypes.c_void_p),
-                     _ptr(grad_out), N, S, M, D, L, S, n_points, _ptr(grad_value), _ptr(grad_proj),
-                     None if ws is None else _ptr(ws), ctypes.c_int64(ws_bytes.value), _stream(value.device))
+        ws_bytes = _native.query("m2f_msda_fused_bwd_workspace", hs, N, S, M, D, L, n_points)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=value.device) if ws_bytes else None
+        _native.call("m2f_msda_fused_bwd_hm_f32" if head_major else "m2f_msda_fused_bwd_f32", value.data_ptr(),
+                     proj.data_ptr(), proj.stride(1), ref.data_ptr(), ref.stride(0), hs, grad_out.data_ptr(), N, S, M,
+                     D, L, S, n_points, grad_value.data_ptr(), grad_proj.data_ptr(), _native.ptr(ws), ws_bytes,
+                     _native.stream(value))
         return grad_value, grad_proj, None, None, None, None
 
 

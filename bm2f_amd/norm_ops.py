@@ -8,17 +8,11 @@ dtypes use the same math in PyTorch (the reference's own CPU behaviour).
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 from torch import nn
 from torch.autograd import Function
 
 from . import _native
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 class AddLayerNorm(Function):
@@ -32,9 +26,9 @@ class AddLayerNorm(Function):
         mean = torch.empty(rows, device=a.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
         w = weight.contiguous()
-        _native.call("m2f_add_layernorm_fwd_f32", a2.data_ptr(), b2.data_ptr() if b2 is not None else None,
-                     w.data_ptr(), bias.contiguous().data_ptr(), ctypes.c_int64(rows), C, ctypes.c_float(eps),
-                     y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _stream(a))
+        _native.call("m2f_add_layernorm_fwd_f32", a2.data_ptr(), _native.ptr(b2),
+                     w.data_ptr(), bias.contiguous().data_ptr(), rows, C, eps,
+                     y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _native.stream(a))
         ctx.save_for_backward(a2, b2, w, mean, rstd)
         ctx.has_b = b is not None
         return y
@@ -49,13 +43,10 @@ class AddLayerNorm(Function):
         need_w, need_b = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         dw = torch.empty(C, device=a.device, dtype=torch.float32) if need_w else None
         db = torch.empty(C, device=a.device, dtype=torch.float32) if need_b else None
-        wsb = ctypes.c_int64(0)
-        _native.call("m2f_add_layernorm_workspace", ctypes.c_int64(rows), C, ctypes.byref(wsb))
-        ws = torch.empty(max(wsb.value, 4), device=a.device, dtype=torch.uint8)
-        _native.call("m2f_add_layernorm_bwd_f32", g.data_ptr(), a.data_ptr(), b.data_ptr() if b is not None else None,
-                     w.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ctypes.c_int64(rows), C, dx.data_ptr(),
-                     dw.data_ptr() if dw is not None else None, db.data_ptr() if db is not None else None,
-                     ws.data_ptr(), ctypes.c_int64(ws.numel()), _stream(a))
+        ws = _native.workspace("m2f_add_layernorm_workspace", rows, C, device=a.device, floor=4)
+        _native.call("m2f_add_layernorm_bwd_f32", g.data_ptr(), a.data_ptr(), _native.ptr(b), w.data_ptr(),
+                     mean.data_ptr(), rstd.data_ptr(), rows, C, dx.data_ptr(), _native.ptr(dw), _native.ptr(db),
+                     ws.data_ptr(), ws.numel(), _native.stream(a))
         # one tensor for both summands, as AddBackward0 does (autograd only accumulates in place into a
         # buffer nothing else references)
         da = dx if ctx.needs_input_grad[0] else None
@@ -78,9 +69,7 @@ def add_layernorm(a: torch.Tensor, b: torch.Tensor | None, norm: nn.LayerNorm) -
 
 
 def _gn_ws(N, C, G, HW, device):
-    b = ctypes.c_int64(0)
-    _native.call("m2f_group_norm_workspace", N, C, G, ctypes.c_int64(HW), ctypes.byref(b))
-    return torch.empty(max(b.value, 16), device=device, dtype=torch.uint8)
+    return _native.workspace("m2f_group_norm_workspace", N, C, G, HW, device=device, floor=16)
 
 
 class GroupNormAct(Function):
@@ -96,10 +85,9 @@ class GroupNormAct(Function):
         mean = torch.empty(N * groups, device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
         ws = _gn_ws(N, C, groups, HW, x.device)
-        _native.call("m2f_group_norm_fwd_f32", x.data_ptr(), weight.data_ptr() if weight is not None else None,
-                     bias.data_ptr() if bias is not None else None, N, C, groups, ctypes.c_int64(HW),
-                     ctypes.c_float(eps), 1 if relu else 0, y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                     ws.data_ptr(), ctypes.c_int64(ws.numel()), _stream(x))
+        _native.call("m2f_group_norm_fwd_f32", x.data_ptr(), _native.ptr(weight), _native.ptr(bias), N, C, groups, HW,
+                     eps, 1 if relu else 0, y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), ws.numel(),
+                     _native.stream(x))
         ctx.save_for_backward(x, weight, bias, mean, rstd)
         ctx.meta = (groups, relu)
         return y
@@ -117,10 +105,8 @@ class GroupNormAct(Function):
         db = torch.empty(C, device=x.device, dtype=torch.float32) if bias is not None and nig[2] else None
         ws = _gn_ws(N, C, groups, HW, x.device)
         _native.call("m2f_group_norm_bwd_f32", g.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                     weight.data_ptr() if weight is not None else None, bias.data_ptr() if bias is not None else None,
-                     N, C, groups, ctypes.c_int64(HW), 1 if relu else 0, dx.data_ptr(),
-                     dw.data_ptr() if dw is not None else None, db.data_ptr() if db is not None else None,
-                     ws.data_ptr(), ctypes.c_int64(ws.numel()), _stream(x))
+                     _native.ptr(weight), _native.ptr(bias), N, C, groups, HW, 1 if relu else 0, dx.data_ptr(),
+                     _native.ptr(dw), _native.ptr(db), ws.data_ptr(), ws.numel(), _native.stream(x))
         return dx, dw, db, None, None, None
 
 

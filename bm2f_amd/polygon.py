@@ -41,8 +41,8 @@ import torch
 
 from . import _native
 from .mask_iou import (_PLANE_ALIGN, MAX_RAGGED_WORDS, _check_size, _decode_plan, _groups_by_offset, _launch_decode,
-                       _launch_pairs, _pack_rows, _pair_counts_ragged_host, _pair_plan, _plane_words, _ptr,
-                       _split_counts, _upload, rle_pair_counts_ragged, rle_to_bits_ragged)
+                       _launch_pairs, _pack_rows, _pair_counts_ragged_host, _pair_plan, _plane_words, _split_counts,
+                       _upload, rle_pair_counts_ragged, rle_to_bits_ragged)
 from .rle import counts_to_string, rle_encode
 
 MAX_COORD = 2.0 ** 26                   # |x|, |y| below this keep 5 x + 0.5 and the edge lengths inside int32
@@ -226,8 +226,9 @@ def _sorted_positions(t, plan, device):
     """The crossings kernel and the one sort -> device int32 positions, polygon after polygon."""
     keys = torch.empty(max(plan.total, 1), dtype=torch.int64, device=device)
     with torch.cuda.device(device):
-        _native.call("m2f_poly_crossings", _ptr(t["poly_edges"]), _ptr(t["poly_slopes"]), _ptr(t["poly_starts"]),
-                     plan.edges.shape[0], plan.total, keys.data_ptr(), torch.cuda.current_stream(device).cuda_stream)
+        _native.call("m2f_poly_crossings", _native.ptr_or_null(t["poly_edges"]), _native.ptr_or_null(t["poly_slopes"]),
+                     _native.ptr_or_null(t["poly_starts"]), plan.edges.shape[0], plan.total, keys.data_ptr(),
+                     _native.stream(device))
     keys = torch.sort(keys[:plan.total])[0]
     return (keys & 0x7fffffff).to(torch.int32)
 
@@ -238,10 +239,11 @@ def _launch_polygons(t, plan, words, device):
         return
     pos = _sorted_positions(t, plan, device)
     with torch.cuda.device(device):
-        _native.call("m2f_poly_decode_bits_ragged", _ptr(pos), pos.numel(), t["poly_pos_offsets"].data_ptr(),
-                     plan.num_polys, t["poly_part_offsets"].data_ptr(), plan.num_anns, t["poly_sizes"].data_ptr(),
-                     t["poly_out_offsets"].data_ptr(), _ptr(t["poly_blocks"]), t["poly_blocks"].numel() // 2,
-                     _ptr(words), words.numel(), torch.cuda.current_stream(device).cuda_stream)
+        _native.call("m2f_poly_decode_bits_ragged", _native.ptr_or_null(pos), pos.numel(),
+                     t["poly_pos_offsets"].data_ptr(), plan.num_polys, t["poly_part_offsets"].data_ptr(), plan.num_anns,
+                     t["poly_sizes"].data_ptr(), t["poly_out_offsets"].data_ptr(),
+                     _native.ptr_or_null(t["poly_blocks"]), t["poly_blocks"].numel() // 2, _native.ptr_or_null(words),
+                     words.numel(), _native.stream(device))
 
 
 def _rasterize(plan, out_offsets, total_words, device):

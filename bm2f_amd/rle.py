@@ -139,10 +139,6 @@ def _char_bound(n, N):
     return 2 * S - max(n - 3, 0)
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _encode_device(src, form, width, plane_index=None, num_masks=None, extra=None):
     """src: a HIP tensor (P, H, row) with unit stride along the row, uint8 / bool (form bytes) or int32 words
     (form bits); mask m is plane plane_index[m] (device int32, clamped by the kernel) or plane m.  ``extra`` is a
@@ -151,8 +147,8 @@ def _encode_device(src, form, width, plane_index=None, num_masks=None, extra=Non
     W = int(width)
     M = P if plane_index is None else int(num_masks)
     dev = src.device
-    st = _stream(src)
-    idx_ptr = None if plane_index is None else plane_index.data_ptr()
+    st = _native.stream(src)
+    idx_ptr = _native.ptr(plane_index)
     geom = (src.data_ptr(), form, idx_ptr, P, M, H, W, src.stride(1), src.stride(0))
     counts = torch.empty(M * W, dtype=torch.int32, device=dev)
     _native.call("m2f_rle_col_counts", *geom, counts.data_ptr(), st)

@@ -13,8 +13,6 @@ same definition in plain torch (roll, partition, matmul, analytic mask), differe
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 import torch.nn.functional as F
 import torch.utils.checkpoint as checkpoint
@@ -26,12 +24,7 @@ from . import _native
 from .registry import BACKBONE_REGISTRY, Backbone, ShapeSpec, register
 
 HEAD_DIM = 32   # every Swin variant; the only head dim the kernels are built for
-_DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 MASKED = -100.0   # reference swin.py:438
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def _pair(v):
@@ -100,9 +93,9 @@ class _WindowAttention(Function):
         out = torch.empty(B, Hp, Wp, C, device=qkv.device, dtype=qkv.dtype)
         lse = torch.empty(B, num_heads, Hp * Wp, device=qkv.device, dtype=torch.float32)
         with torch.cuda.device(qkv.device):   # the launch goes to the tensors' device, current or not
-            _native.call("m2f_window_attn_fwd", _DTYPE_CODE[qkv.dtype], qkv.data_ptr(), table.data_ptr(), B,
-                         num_heads, C // num_heads, Hp, Wp, window_size, shift, ctypes.c_float(scale),
-                         out.data_ptr(), lse.data_ptr(), _stream(qkv))
+            _native.call("m2f_window_attn_fwd", _native.dtype_code(qkv.dtype, "window_attention"), qkv.data_ptr(),
+                         table.data_ptr(), B, num_heads, C // num_heads, Hp, Wp, window_size, shift, scale,
+                         out.data_ptr(), lse.data_ptr(), _native.stream(qkv))
         ctx.save_for_backward(qkv, table, lse)
         ctx.meta = (num_heads, window_size, shift, scale, bias_table.dtype)
         return out
@@ -119,16 +112,13 @@ class _WindowAttention(Function):
         grad = grad.contiguous()
         dqkv = torch.empty_like(qkv)
         dtable = torch.empty_like(table)
-        nbytes = ctypes.c_int64(0)
-        _native.call("m2f_window_attn_workspace", B, nH, Hp, Wp, ws, ctypes.byref(nbytes))
-        work = torch.empty(max(nbytes.value, 16), device=qkv.device, dtype=torch.uint8)
+        work = _native.workspace("m2f_window_attn_workspace", B, nH, Hp, Wp, ws, device=qkv.device, floor=16)
         # one kernel produces both gradients (the table's falls out of the dS it computes for dqkv anyway); a
         # gradient nobody asked for is dropped here
         with torch.cuda.device(qkv.device):
-            _native.call("m2f_window_attn_bwd", _DTYPE_CODE[qkv.dtype], qkv.data_ptr(), table.data_ptr(),
-                         grad.data_ptr(), lse.data_ptr(), B, nH, C3 // (3 * nH), Hp, Wp, ws, shift,
-                         ctypes.c_float(scale), dqkv.data_ptr(), dtable.data_ptr(), work.data_ptr(),
-                         ctypes.c_int64(work.numel()), _stream(qkv))
+            _native.call("m2f_window_attn_bwd", _native.dtype_code(qkv.dtype, "window_attention"), qkv.data_ptr(),
+                         table.data_ptr(), grad.data_ptr(), lse.data_ptr(), B, nH, C3 // (3 * nH), Hp, Wp, ws, shift,
+                         scale, dqkv.data_ptr(), dtable.data_ptr(), work.data_ptr(), work.numel(), _native.stream(qkv))
         return (dqkv if need_qkv else None, dtable.to(table_dtype) if need_table else None, None, None, None, None)
 
 
@@ -153,7 +143,7 @@ def window_attention(qkv, bias_table, num_heads, window_size, shift, scale=None)
     scale = float(head_dim ** -0.5 if scale is None else scale)
     if not qkv.is_cuda:
         return window_attention_torch(qkv, bias_table, num_heads, ws, int(shift), scale)
-    if qkv.dtype not in _DTYPE_CODE:
+    if qkv.dtype not in _native.DTYPE_CODES:
         raise TypeError(f"window_attention on the device takes fp32, fp16 or bf16, got {qkv.dtype}")
     # an unsupported window size or head dim is refused by the library (NativeError): there is no other device path
     return _WindowAttention.apply(qkv, bias_table, num_heads, ws, int(shift), scale)

@@ -27,7 +27,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _native
-from .inference import _code, _geometry, _pair, _stream, full_resolution_logits
+from .inference import _geometry, _pair, full_resolution_logits
 from .rle import _BITS, _encode_device, rle_encode
 
 
@@ -73,15 +73,17 @@ def _video_masks_hip(mask_pred, qidx, scores, labels, padded_size, geo, packed, 
     buf[words:words + k] = scores.float().view(torch.int32)
     buf[words + k:words + 2 * k] = labels.to(torch.int32)
     buf[words + 2 * k:] = slot.to(torch.int32)
-    _native.call("m2f_infer_video", masks.data_ptr(), _code(masks), sel.data_ptr(), n_sel.data_ptr(), Q, S, T, h, w,
-                 Hp, Wp, Hc, Wc, Ho, Wo, int(packed), buf.data_ptr(), _stream(masks))
+    _native.call("m2f_infer_video", masks.data_ptr(), _native.dtype_code(masks.dtype, "video inference masks"),
+                 sel.data_ptr(), n_sel.data_ptr(), Q, S, T, h, w, Hp, Wp, Hc, Wc, Ho, Wo, int(packed), buf.data_ptr(),
+                 _native.stream(masks))
     bits = None
     if keep_bits and packed:
         bits = buf[:body].view(S, T, Ho, row)
     elif keep_bits:                                                         # the byte form holds no planes: a second launch
         bits = torch.empty((S, T, Ho, (Wo + 31) // 32), dtype=torch.int32, device=dev)
-        _native.call("m2f_infer_video", masks.data_ptr(), _code(masks), sel.data_ptr(), n_sel.data_ptr(), Q, S, T,
-                     h, w, Hp, Wp, Hc, Wc, Ho, Wo, 1, bits.data_ptr(), _stream(masks))
+        _native.call("m2f_infer_video", masks.data_ptr(), _native.dtype_code(masks.dtype, "video inference masks"),
+                     sel.data_ptr(), n_sel.data_ptr(), Q, S, T, h, w, Hp, Wp, Hc, Wc, Ho, Wo, 1, bits.data_ptr(),
+                     _native.stream(masks))
     host = buf.cpu()                                                        # the head's one synchronisation
     tail = host[words:]
     if packed:
@@ -106,8 +108,9 @@ def _video_rle_hip(mask_pred, qidx, scores, labels, padded_size, geo, keep_bits=
     S = min(Q, k)
     slot, sel, n_sel = _select_slots(Q, S, qidx)
     bits = torch.empty((S * T, Ho, (Wo + 31) // 32), dtype=torch.int32, device=dev)
-    _native.call("m2f_infer_video", masks.data_ptr(), _code(masks), sel.data_ptr(), n_sel.data_ptr(), Q, S, T, h, w,
-                 Hp, Wp, Hc, Wc, Ho, Wo, 1, bits.data_ptr(), _stream(masks))
+    _native.call("m2f_infer_video", masks.data_ptr(), _native.dtype_code(masks.dtype, "video inference masks"),
+                 sel.data_ptr(), n_sel.data_ptr(), Q, S, T, h, w, Hp, Wp, Hc, Wc, Ho, Wo, 1, bits.data_ptr(),
+                 _native.stream(masks))
     # slots >= n_sel were not written: they are encoded from slot 0 and never indexed
     live = torch.arange(S, device=dev)
     live = torch.where(live < n_sel, live, torch.zeros_like(live))

@@ -22,7 +22,7 @@ import torch.nn.functional as F
 
 from . import _native
 from . import weaksup as ws
-from .inference import _code, _pair
+from .inference import _pair
 
 
 def _frames(clip, num_frames):
@@ -70,8 +70,8 @@ def feat_resize_pad(feats: torch.Tensor, padded_size, out_size) -> torch.Tensor:
         out = torch.empty(lead + (oh, ow), dtype=torch.float32, device=x.device)
         planes = x.numel() // (Hs * Ws)
         if planes:
-            _native.call("m2f_feat_resize_pad", x.data_ptr(), _code(x), planes, Hs, Ws, Hp, Wp, oh, ow, out.data_ptr(),
-                         torch.cuda.current_stream(x.device).cuda_stream)
+            _native.call("m2f_feat_resize_pad", x.data_ptr(), _native.dtype_code(x.dtype, "feat_resize_pad"), planes,
+                         Hs, Ws, Hp, Wp, oh, ow, out.data_ptr(), _native.stream(x))
         return out
     x = F.pad(feats.double().reshape(1, -1, Hs, Ws), (0, Wp - Ws, 0, Hp - Hs))
     return F.interpolate(x, size=(oh, ow), mode="bilinear", align_corners=False).float().reshape(lead + (oh, ow))

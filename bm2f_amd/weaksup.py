@@ -11,7 +11,6 @@ their definition in plain torch on CPU tensors, like ``inference.py``.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import List, Sequence
 
 import torch
@@ -20,18 +19,10 @@ from torch.autograd import Function
 from . import _native
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _need_cuda(*ts):
     for t in ts:
         if t is not None and not t.is_cuda:
             raise RuntimeError("bm2f_amd.weaksup ops need CUDA (HIP) tensors; there is no CPU path")
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def h2d(values: Sequence[int], device, dtype=torch.int32) -> torch.Tensor:
@@ -66,8 +57,8 @@ def lsap_batched(cost: torch.Tensor, cols: torch.Tensor | None = None, rows: tor
     status = torch.zeros((B,), dtype=torch.int32, device=dev)
     if B == 0 or R == 0:
         return match, status
-    _native.call("m2f_lsap_batched", c.data_ptr(), B, R, C, ctypes.c_int64(R * C), rows.data_ptr(), _ptr(cols),
-                 match.data_ptr(), status.data_ptr(), _stream(c))
+    _native.call("m2f_lsap_batched", c.data_ptr(), B, R, C, R * C, rows.data_ptr(), _native.ptr(cols),
+                 match.data_ptr(), status.data_ptr(), _native.stream(c))
     return match, status
 
 
@@ -104,8 +95,7 @@ def threshold_bits(sim: torch.Tensor, thr: float) -> torch.Tensor:
     s = sim.float().contiguous()
     N, _, H, W = s.shape
     bits = torch.empty((N, H, W), dtype=torch.uint8, device=s.device)
-    _native.call("m2f_threshold_bits", s.data_ptr(), N, ctypes.c_int64(H * W), ctypes.c_float(thr), bits.data_ptr(),
-                 _stream(s))
+    _native.call("m2f_threshold_bits", s.data_ptr(), N, H * W, thr, bits.data_ptr(), _native.stream(s))
     return bits
 
 
@@ -130,7 +120,7 @@ def pairwise_map(x: torch.Tensor, bits: torch.Tensor, t_row: torch.Tensor, dilat
     N, H, W = x.shape
     out = torch.empty((N, H, W), dtype=torch.float32, device=x.device)
     _native.call("m2f_pairwise_rows", x.data_ptr(), None, N, H, W, dilation, bits.data_ptr(), t_row.data_ptr(), None,
-                 None, 0, out.data_ptr(), None, _stream(x))
+                 None, 0, out.data_ptr(), None, _native.stream(x))
     return out
 
 
@@ -140,7 +130,7 @@ def pairwise_planes(x: torch.Tensor, dilation: int) -> torch.Tensor:
     N, H, W = x.shape
     out = torch.empty((N, 8, H, W), dtype=torch.float32, device=x.device)
     _native.call("m2f_pairwise_rows", x.data_ptr(), None, N, H, W, dilation, None, None, None, None, 2, out.data_ptr(),
-                 None, _stream(x))
+                 None, _native.stream(x))
     return out
 
 
@@ -182,7 +172,7 @@ def match_cost(x: torch.Tensor, bits: torch.Tensor, box: torch.Tensor, gcount: t
     cmax = torch.empty((B * Q, nty, W), dtype=torch.float32, device=x.device)
     _native.call("m2f_pairwise_match_cost", x.data_ptr(), B, Q, H, W, dilation, bits.data_ptr(), box.data_ptr(),
                  gcount.data_ptr(), extents.data_ptr(), Gm, part.data_ptr(), rmax.data_ptr(), cmax.data_ptr(),
-                 _stream(x))
+                 _native.stream(x))
     return (part.sum(1).view(B, Q, Gm), rmax.amax(2).view(B, Q, H), cmax.amax(1).view(B, Q, W))
 
 
@@ -199,8 +189,9 @@ class PairwiseSums(Function):
         num = torch.empty((N, max(tiles, 1)), dtype=torch.float32, device=x.device)
         den = torch.empty_like(num)
         if N and H and W:
-            _native.call("m2f_pairwise_rows", x.data_ptr(), None, N, H, W, dilation, bits.data_ptr(), _ptr(t_row),
-                         _ptr(box), _ptr(box_row), 1, num.data_ptr(), den.data_ptr(), _stream(x))
+            _native.call("m2f_pairwise_rows", x.data_ptr(), None, N, H, W, dilation, bits.data_ptr(),
+                         _native.ptr(t_row), _native.ptr(box), _native.ptr(box_row), 1, num.data_ptr(), den.data_ptr(),
+                         _native.stream(x))
         else:
             num.zero_()
             den.zero_()
@@ -218,7 +209,8 @@ class PairwiseSums(Function):
         if N and H and W:
             g = g_num.float().contiguous()
             _native.call("m2f_pairwise_rows_bwd", x.data_ptr(), None, N, H, W, ctx.dilation, bits.data_ptr(),
-                         _ptr(t_row), _ptr(box), _ptr(box_row), g.data_ptr(), grad.data_ptr(), _stream(x))
+                         _native.ptr(t_row), _native.ptr(box), _native.ptr(box_row), g.data_ptr(), grad.data_ptr(),
+                         _native.stream(x))
         return grad, None, None, None, None, None
 
 
@@ -321,7 +313,7 @@ def temporal_pairs(feats: torch.Tensor, boxes: torch.Tensor, k: int = 1) -> Mine
             seg_d = _from_host(np.asarray(segs, np.int32), dev)
             blk_d = _from_host(np.asarray(blocks, np.int32), dev)
             _native.call("m2f_temporal_mine", x.data_ptr(), T, D, h, w, seg_d.data_ptr(), len(segs), blk_d.data_ptr(),
-                         len(blocks), p1.data_ptr(), off, _stream(x))
+                         len(blocks), p1.data_ptr(), off, _native.stream(x))
     else:
         parts = []
         for (t, cx0, cy0, cw, nc, nx0, ny0, nw, nn, _) in segs:
@@ -425,7 +417,7 @@ class TemporalPairSum(Function):
         part_cnt = torch.empty(nb, dtype=torch.int32, device=src.device)
         _native.call("m2f_temporal_pairs_fwd", src.data_ptr(), N, T, H, W, row_of_target.data_ptr(), pk.n_targets,
                      pk.row.data_ptr(), pk.t.data_ptr(), pk.p0.data_ptr(), pk.p1.data_ptr(), pk.P,
-                     part_sum.data_ptr(), part_cnt.data_ptr(), _stream(src))
+                     part_sum.data_ptr(), part_cnt.data_ptr(), _native.stream(src))
         ctx.save_for_backward(src, row_of_target)
         ctx.pk = pk
         total, count = part_sum.sum(), part_cnt.sum()
@@ -441,7 +433,7 @@ class TemporalPairSum(Function):
         g = g_total.float().reshape(1).contiguous()
         _native.call("m2f_temporal_pairs_bwd", src.data_ptr(), N, T, H, W, row_of_target.data_ptr(), pk.n_targets,
                      pk.row.data_ptr(), pk.t.data_ptr(), pk.p0.data_ptr(), pk.p1.data_ptr(), pk.P,
-                     pk.ep_key.data_ptr(), pk.ep_code.data_ptr(), g.data_ptr(), grad.data_ptr(), _stream(src))
+                     pk.ep_key.data_ptr(), pk.ep_code.data_ptr(), g.data_ptr(), grad.data_ptr(), _native.stream(src))
         return grad, None, None
 
 
@@ -480,7 +472,7 @@ def images_lab(images: torch.Tensor, stride: int) -> torch.Tensor:
     if C != 3:
         raise ValueError("images must have 3 channels")
     lab = torch.empty((B, 3, Hp // stride, Wp // stride), dtype=torch.float32, device=x.device)
-    _native.call("m2f_weaksup_lab", x.data_ptr(), B, Hp, Wp, stride, lab.data_ptr(), _stream(x))
+    _native.call("m2f_weaksup_lab", x.data_ptr(), B, Hp, Wp, stride, lab.data_ptr(), _native.stream(x))
     return lab
 
 
@@ -492,7 +484,7 @@ def color_similarity(lab: torch.Tensor, mask: torch.Tensor, dilation: int) -> to
     B, _, h, w = lab.shape
     sim = torch.empty((B, 8, h, w), dtype=torch.float32, device=lab.device)
     _native.call("m2f_color_similarity", lab.data_ptr(), mask.data_ptr(), B, h, w, dilation, sim.data_ptr(),
-                 _stream(lab))
+                 _native.stream(lab))
     return sim
 
 

@@ -23,6 +23,59 @@ def test_library_exports_header_symbols():
     assert lib.m2f_last_error() == b""
 
 
+def _header():
+    """include/bm2f.h without its comments."""
+    src = open(os.path.join(ROOT, "include", "bm2f.h")).read()
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+
+
+_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
+
+
+def _kind(param, where):
+    """The ctypes kind of one C parameter declaration; an unknown type fails the test."""
+    words = param.replace("*", " * ").split()
+    if "*" in words:
+        if words.count("*") == 1 and words[:words.index("*")] == ["const", "char"]:
+            return ctypes.c_char_p
+        return ctypes.c_void_p
+    types = [w for w in words[:-1] if w != "const"]          # the last word is the parameter's name
+    assert len(types) == 1 and types[0] in _SCALARS, f"{where}: unknown parameter type in {param!r}"
+    return _SCALARS[types[0]]
+
+
+def _prototypes():
+    """{name: [kind, ...]} of every ``int m2f_*(...)`` prototype of the header."""
+    out = {}
+    for name, params in re.findall(r"\bint\s+(m2f_\w+)\s*\(([^)]*)\)\s*;", _header()):
+        assert name not in out, f"{name} is declared twice"
+        params = params.strip()
+        out[name] = [] if params in ("", "void") else [_kind(p, name) for p in params.split(",")]
+    return out
+
+
+def test_signature_table_matches_header():
+    """_native._SIGNATURES is the only thing between a Python int and the width of a C parameter: every entry must
+    equal its prototype in include/bm2f.h, kind for kind, and the two must hold the same names."""
+    from bm2f_amd import _native
+    protos = _prototypes()
+    assert protos.pop("m2f_abi_version") == []               # declared by hand in load(), like m2f_last_error
+    assert "m2f_last_error" not in protos and re.search(r"const\s+char\s*\*\s*m2f_last_error\s*\(\s*void\s*\)", _header())
+    assert len(protos) >= 90
+    assert set(protos) == set(_native._SIGNATURES)
+    for name, kinds in protos.items():
+        assert kinds == _native._SIGNATURES[name], name
+
+
+def test_dtype_codes_match_header():
+    import torch
+    from bm2f_amd import _native
+    enum = dict(re.findall(r"\b(M2F_(?:F32|F16|BF16))\s*=\s*(\d+)", _header()))
+    assert set(enum) == {"M2F_F32", "M2F_F16", "M2F_BF16"}
+    assert _native.DTYPE_CODES == {torch.float32: int(enum["M2F_F32"]), torch.float16: int(enum["M2F_F16"]),
+                                   torch.bfloat16: int(enum["M2F_BF16"])}
+
+
 def test_invalid_args_report_errors_without_gpu():
     from bm2f_amd import _native
     lib = _native.load()

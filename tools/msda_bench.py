@@ -55,7 +55,6 @@ def fused_calls(value, shapes, gout, noise, M=8, P=4, seed=1):
     """Forward / backward closures of the fused-front-end kernels (m2f_msda_fused_{fwd,bwd}_f32) on the
     encoder layout: reference points at the pixel centres, offsets on the reference init rays (pixel units,
     ms_deform_attn.py:_reset_parameters) plus N(0, noise) px, random logits."""
-    import ctypes
     from bm2f_amd import _native
     N, S = value.shape[:2]
     L = len(shapes)
@@ -80,21 +79,22 @@ def fused_calls(value, shapes, gout, noise, M=8, P=4, seed=1):
     out = torch.empty(N, S, M * 32, device=dev)
     gv = torch.empty_like(value)
     gp = torch.empty_like(proj)
-    st = msda._stream(dev)
+    st = _native.stream(dev)
     D = value.shape[-1]
 
     def fwd():
-        _native.call("m2f_msda_fused_fwd_hm_f32" if HEAD_MAJOR else "m2f_msda_fused_fwd_f32", msda._ptr(value), msda._ptr(proj), proj.stride(1), msda._ptr(ref),
-                     ref.stride(0), ctypes.cast(hs, ctypes.c_void_p), N, S, M, D, L, S, P, msda._ptr(out), st)
+        _native.call("m2f_msda_fused_fwd_hm_f32" if HEAD_MAJOR else "m2f_msda_fused_fwd_f32", value.data_ptr(),
+                     proj.data_ptr(), proj.stride(1), ref.data_ptr(), ref.stride(0), hs, N, S, M, D, L, S, P,
+                     out.data_ptr(), st)
 
-    wsb = ctypes.c_int64(0)  # deterministic mode (--opt msda_bwd_det=1) needs a workspace
-    _native.call("m2f_msda_fused_bwd_workspace", ctypes.cast(hs, ctypes.c_void_p), N, S, M, D, L, P, ctypes.byref(wsb))
-    ws = torch.empty(wsb.value, dtype=torch.uint8, device=dev) if wsb.value else None
+    # deterministic mode (--opt msda_bwd_det=1) needs a workspace
+    ws_bytes = _native.query("m2f_msda_fused_bwd_workspace", hs, N, S, M, D, L, P)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
 
     def bwd():
-        _native.call("m2f_msda_fused_bwd_hm_f32" if HEAD_MAJOR else "m2f_msda_fused_bwd_f32", msda._ptr(value), msda._ptr(proj), proj.stride(1), msda._ptr(ref),
-                     ref.stride(0), ctypes.cast(hs, ctypes.c_void_p), msda._ptr(gout), N, S, M, D, L, S, P,
-                     msda._ptr(gv), msda._ptr(gp), None if ws is None else msda._ptr(ws), ctypes.c_int64(wsb.value), st)
+        _native.call("m2f_msda_fused_bwd_hm_f32" if HEAD_MAJOR else "m2f_msda_fused_bwd_f32", value.data_ptr(),
+                     proj.data_ptr(), proj.stride(1), ref.data_ptr(), ref.stride(0), hs, gout.data_ptr(), N, S, M, D, L,
+                     S, P, gv.data_ptr(), gp.data_ptr(), _native.ptr(ws), ws_bytes, st)
     fwd.tensors = {"out": out, "grad_value": gv, "grad_proj": gp, "M": M, "LP": len(shapes) * P}
     return fwd, bwd
 

@@ -41,7 +41,7 @@ sys.path.insert(0, ROOT)
 from bm2f_amd import (COCOPanopticEvaluator, PanopticGroundTruth, SemSegEvaluator,  # noqa: E402
                       label_pair_counts_ragged)
 from bm2f_amd import _native, label_counts  # noqa: E402
-from bm2f_amd.mask_iou import _ptr, _upload  # noqa: E402
+from bm2f_amd.mask_iou import _upload  # noqa: E402
 
 HBM_BYTES_PER_S = 8e12
 OFFSET = 256 ** 3
@@ -104,9 +104,9 @@ def kernel_window(a_planes, b_planes, rows, cols, ignore, ids, share, path, reps
     d = _upload({"images": images, "ids": flat_ids, "blocks": blocks}, dev)
     out = torch.zeros(out_len + G, dtype=torch.int64, device=dev)
     args = (fa.data_ptr(), fa.element_size(), fa.numel(), fb.data_ptr(), fb.element_size(), fb.numel(),
-            d["images"].data_ptr(), G, _ptr(d["ids"]), flat_ids.size, d["blocks"].data_ptr(), blocks.shape[0],
-            int(ignore is not None), ignore or 0, int(bins.max()), {"auto": 0, "lds": 1, "global": 2}[path],
-            out.data_ptr(), out_len, out.data_ptr() + 8 * out_len, torch.cuda.current_stream(dev).cuda_stream)
+            d["images"].data_ptr(), G, _native.ptr_or_null(d["ids"]), flat_ids.size, d["blocks"].data_ptr(),
+            blocks.shape[0], int(ignore is not None), ignore or 0, int(bins.max()), {"auto": 0, "lds": 1, "global": 2}[path],
+            out.data_ptr(), out_len, out.data_ptr() + 8 * out_len, _native.stream(dev))
     ms = launch_window_ms(lambda: _native.call("m2f_label_pair_counts_ragged", *args), reps)
     return ms, fa.numel() * fa.element_size() + fb.numel() * fb.element_size(), int(blocks.shape[0])
 
