@@ -39,6 +39,9 @@ inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_
 
 inline unsigned ceil_div(int64_t a, int64_t b) { return static_cast<unsigned>((a + b - 1) / b); }
 
+// one of the three floating-point element types of the C ABI
+inline bool is_float_dtype(int dtype) { return dtype == M2F_F32 || dtype == M2F_F16 || dtype == M2F_BF16; }
+
 // Explicit tuning options (m2f_set_option, include/bm2f.h): geometry and engine overrides for tests and
 // tools.  The library never reads the environment; an unset option means the built-in default.  Every
 // option changes the partition or the kernel variant only, never the arithmetic's result.

@@ -48,11 +48,6 @@ __device__ __forceinline__ float hi16(unsigned u) {
   else
     return __uint_as_float(u & 0xffff0000u);
 }
-template <typename TI>
-__device__ __forceinline__ float to_f(TI v) {
-  if constexpr (std::is_same<TI, float>::value) return v;
-  else return static_cast<float>(v);
-}
 // two floats -> one word of two 16-bit values (element 0 in the low half)
 template <typename TO>
 __device__ __forceinline__ unsigned pack2(float a, float b) {
@@ -71,7 +66,7 @@ struct ARaw {
   }
   __device__ __forceinline__ void get(float (&x)[8]) const {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) x[e] = to_f(v[e]);
+    for (int e = 0; e < 8; ++e) x[e] = m2f::Elt<TI>::to_f(v[e]);
   }
 };
 template <typename TI>

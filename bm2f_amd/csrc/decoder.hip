@@ -15,44 +15,25 @@
 //   A: lane holds A[row r][k = kw*g + j]   B: lane holds B[k = kw*g + j][col r]   (kw = 4 for 16-bit, 1 for f32)
 //   C: lane holds C[row 4*g + i][col r], i = 0..3
 #include "common.h"
+#include "device_util.h"
 
 #include <cmath>
 #include <cstdlib>
 
 namespace {
 
-using f4 = float __attribute__((ext_vector_type(4)));
-using s4 = short __attribute__((ext_vector_type(4)));
+using m2f::bf8, m2f::f4, m2f::h8, m2f::s4, m2f::s8, m2f::Elt, m2f::kLog2e, m2f::tr_read;
 using h4 = _Float16 __attribute__((ext_vector_type(4)));
-using lds_s4 = __attribute__((address_space(3))) s4;
 
 constexpr int kD = 32;       // head dim (hidden 256 / 8 heads)
 constexpr float kLazyLog2 = 8.f;   // forward: rescale when a block max exceeds the running max by 2^8
 constexpr int kDQ = kD + 1;   // row pitch of the register-dQ reductions' LDS image (floats): at most 2-way bank
                               // conflicts (a pitch of kD puts the 16 lanes of a column group on one bank)
 constexpr int kDP = kD + 4;  // padded LDS row (elements) for 16-bit images: 72 B rows, 8 B aligned
-constexpr float kLog2e = 1.4426950408889634f;
 
 // ----------------------------------------------------------------------------------------------
-// element traits
+// MFMA selectors on the element traits of device_util.h
 // ----------------------------------------------------------------------------------------------
-template <typename T> struct Elt;
-template <> struct Elt<float> {
-  static constexpr bool k16 = false;
-  __device__ static float to_f(float x) { return x; }
-  __device__ static float from_f(float x) { return x; }
-};
-template <> struct Elt<__bf16> {
-  static constexpr bool k16 = true;
-  __device__ static float to_f(__bf16 x) { return static_cast<float>(x); }
-  __device__ static __bf16 from_f(float x) { return static_cast<__bf16>(x); }
-};
-template <> struct Elt<_Float16> {
-  static constexpr bool k16 = true;
-  __device__ static float to_f(_Float16 x) { return static_cast<float>(x); }
-  __device__ static _Float16 from_f(float x) { return static_cast<_Float16>(x); }
-};
-
 template <typename T>
 __device__ __forceinline__ f4 mma16(s4 a, s4 b, f4 c) {
   if constexpr (std::is_same<T, _Float16>::value)
@@ -67,15 +48,12 @@ __device__ __forceinline__ f4 mma32(float a, float b, f4 c) {
 
 // gfx950's 16x16x32 forms (twice the K of 16x16x16 per instruction): lane 16g + r holds A[row r][k = 8g + j] and
 // B[k = 8g + j][col r], j = 0..7
-using s8 = short __attribute__((ext_vector_type(8)));
-using h8 = _Float16 __attribute__((ext_vector_type(8)));
-using b8 = __bf16 __attribute__((ext_vector_type(8)));
 template <typename T>
 __device__ __forceinline__ f4 mmak32(s8 a, s8 b, f4 c) {
   if constexpr (std::is_same<T, _Float16>::value)
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
   else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8, a), __builtin_bit_cast(b8, b), c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8, a), __builtin_bit_cast(bf8, b), c, 0, 0, 0);
 }
 __device__ __forceinline__ s8 cat8(s4 lo, s4 hi) { return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7); }
 
@@ -100,13 +78,6 @@ template <typename T>
 __device__ __forceinline__ s4 pack4(float a, float b, float c, float d) {
   T t[4] = {Elt<T>::from_f(a), Elt<T>::from_f(b), Elt<T>::from_f(c), Elt<T>::from_f(d)};
   return *reinterpret_cast<s4*>(t);
-}
-
-// Transposed 4x16 read: lane 4q+p of each 16-lane group passes the address of row q, columns
-// 4p..4p+3 of its block; lane i receives column i of the 4 rows (row q in element q).
-__device__ __forceinline__ s4 tr_read(const void* lds_ptr) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (lds_s4*)(reinterpret_cast<uintptr_t>(lds_ptr)));
 }
 
 // Reduce over the 4 lane groups (same r) with gfx950's row-swap moves (VALU; __shfl_xor is an LDS permute with

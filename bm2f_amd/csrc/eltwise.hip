@@ -47,7 +47,7 @@ extern "C" int m2f_bias_act_nchw(void* x, const void* residual, const float* bia
                                  int dtype, int channels_last, void* stream) {
   const char* fn = "m2f_bias_act_nchw";
   if (!x || !bias || N < 0 || C <= 0 || HW <= 0) return m2f::fail(M2F_EINVAL, "%s: bad arguments", fn);
-  if (dtype != M2F_BF16 && dtype != M2F_F16 && dtype != M2F_F32)
+  if (!m2f::is_float_dtype(dtype))
     return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
   const int V = dtype == M2F_F32 ? 4 : 8;
   if ((channels_last ? C % V : HW % V) || !m2f::aligned(x, 16) || (residual && !m2f::aligned(residual, 16)))
@@ -114,7 +114,7 @@ extern "C" int m2f_relu_bwd_sum(const void* const* grads, int ngrads, const void
   const char* fn = "m2f_relu_bwd_sum";
   if (!grads || ngrads < 1 || ngrads > kMaxReluGrads || !y || !out || n < 0)
     return m2f::fail(M2F_EINVAL, "%s: bad arguments (1 <= grads <= %d)", fn, kMaxReluGrads);
-  if (dtype != M2F_BF16 && dtype != M2F_F16 && dtype != M2F_F32)
+  if (!m2f::is_float_dtype(dtype))
     return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
   const int V = dtype == M2F_F32 ? 4 : 8;
   ReluGrads gs{};
@@ -181,7 +181,7 @@ extern "C" int m2f_sum_to_f32(const void* const* srcs, int k, int64_t n, int dty
   const char* fn = "m2f_sum_to_f32";
   if (!srcs || k < 1 || k > kMaxSumTerms || !out || n < 0)
     return m2f::fail(M2F_EINVAL, "%s: bad arguments (1 <= terms <= %d)", fn, kMaxSumTerms);
-  if (dtype != M2F_BF16 && dtype != M2F_F16 && dtype != M2F_F32)
+  if (!m2f::is_float_dtype(dtype))
     return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
   const int V = 8;
   SumTerms ts{};
@@ -463,7 +463,7 @@ extern "C" int m2f_maxpool3s2_bwd(const void* grad_y, const uint8_t* window, voi
   const int64_t total = planes * H * W;
   if (total == 0) return m2f::ok();
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (W % 8 == 0 && m2f::aligned(grad_x, 16) && (dtype == M2F_BF16 || dtype == M2F_F16 || dtype == M2F_F32)) {
+  if (W % 8 == 0 && m2f::aligned(grad_x, 16) && m2f::is_float_dtype(dtype)) {
     const int64_t total8 = total / 8;
     const unsigned g8 = m2f::ceil_div(total8, 256);
     if (dtype == M2F_BF16)

@@ -18,6 +18,7 @@
 // products are the same; only the order of the fp32 fma chain differs from a k-sequential loop.
 #include "bm2f.h"
 #include "common.h"
+#include "device_util.h"
 
 #include <hip/hip_runtime.h>
 
@@ -26,22 +27,11 @@
 
 namespace {
 
-using f4 = float __attribute__((ext_vector_type(4)));
-using f16v = float __attribute__((ext_vector_type(16)));
+using m2f::f16v, m2f::f4, m2f::mfma32, m2f::xcd_remap;
 
 constexpr int kBM = 128, kBN = 128, kBK = 32;
 constexpr int kPitch = kBK + 4;  // floats per LDS row: 144 B, conflict-free ds_read_b128 over 8 rows
 constexpr int kThreads = 256;
-
-__device__ __forceinline__ f16v mfma32(float a, float b, f16v c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
-// bijective XCD-aware remap: consecutive logical ids land on the same XCD (blocks id, id+8, ... share one)
-__device__ __forceinline__ int xcd_remap(int id, int nwg) {
-  const int q = nwg / 8, r = nwg % 8, xcd = id % 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + id / 8;
-}
 
 enum Epi { kNone = 0, kBias = 1, kRelu = 2, kMask = 4 };
 

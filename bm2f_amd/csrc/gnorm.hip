@@ -12,6 +12,7 @@
 //             1 write per element).
 #include "bm2f.h"
 #include "common.h"
+#include "device_util.h"
 
 #include <hip/hip_runtime.h>
 
@@ -19,7 +20,7 @@
 
 namespace {
 
-using f4 = float __attribute__((ext_vector_type(4)));
+using m2f::f4;
 
 constexpr int kT = 256;
 

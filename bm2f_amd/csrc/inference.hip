@@ -38,9 +38,7 @@ namespace {
 using m2f::AxisTaps;
 using m2f::Geo;
 using m2f::Tap;
-
-using f4 = float __attribute__((ext_vector_type(4)));
-using f16v = float __attribute__((ext_vector_type(16)));
+using m2f::f16v, m2f::f4, m2f::wave_sum;
 
 constexpr int kMaxQ = 256, kMaxK = 256;
 constexpr int kTH = 4, kTW = 32, kPix = kTH * kTW;  // semantic pixel tile: wave w owns row w
@@ -168,7 +166,7 @@ __global__ void __launch_bounds__(256) semantic_kernel(const void* __restrict__ 
       for (int i = 0; i < KT; ++i) {
         const f4 fa = *reinterpret_cast<const f4*>(&sA[(i * 32 + li) * kP + kk * 8 + lh * 4]);
 #pragma unroll
-        for (int s = 0; s < 4; ++s) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[s], fb[s], acc[i], 0, 0, 0);
+        for (int s = 0; s < 4; ++s) acc[i] = m2f::mfma32(fa[s], fb[s], acc[i]);
       }
     }
     __syncthreads();
@@ -274,12 +272,6 @@ __global__ void __launch_bounds__(256) panoptic_kernel(const void* __restrict__ 
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int kInstTile = 1024;
 
-__device__ __forceinline__ float wave_sum_fixed(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 __global__ void __launch_bounds__(256) instance_kernel(const void* __restrict__ logits, int dtype,
                                                        const int32_t* __restrict__ sel_idx,
                                                        const int32_t* __restrict__ num_sel,
@@ -316,8 +308,8 @@ __global__ void __launch_bounds__(256) instance_kernel(const void* __restrict__ 
       }
     }
   }
-  sum = wave_sum_fixed(sum);
-  count = wave_sum_fixed(count);
+  sum = wave_sum(sum);  // fixed butterfly order, then the fixed wave order below: bitwise repeatable partials
+  count = wave_sum(count);
   if ((tid & 63) == 0) {
     red[0][tid >> 6] = sum;
     red[1][tid >> 6] = count;
@@ -339,8 +331,8 @@ __global__ void __launch_bounds__(64) instance_combine_kernel(const float* __res
     sum += part[t * 2];
     count += part[t * 2 + 1];
   }
-  sum = wave_sum_fixed(sum);
-  count = wave_sum_fixed(count);
+  sum = wave_sum(sum);  // the fixed butterfly of the comment above: the order is part of the result
+  count = wave_sum(count);
   if (threadIdx.x == 0) {
     sums[row * 2] = sum;
     sums[row * 2 + 1] = count;
@@ -350,7 +342,7 @@ __global__ void __launch_bounds__(64) instance_combine_kernel(const float* __res
 int check_common(const char* fn, const void* logits, int dtype, const int32_t* sizes, int batch, int Q, int h, int w,
                  int Hp, int Wp, int out_h, int out_w) {
   if (!logits || !sizes) return m2f::fail(M2F_EINVAL, "%s: null pointer", fn);
-  if (dtype != M2F_F32 && dtype != M2F_F16 && dtype != M2F_BF16) return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
+  if (!m2f::is_float_dtype(dtype)) return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
   if (batch <= 0 || Q <= 0 || h <= 0 || w <= 0 || Hp <= 0 || Wp <= 0 || out_h <= 0 || out_w <= 0)
     return m2f::fail(M2F_EINVAL, "%s: sizes must be positive", fn);
   if (Q > kMaxQ) return m2f::fail(M2F_EUNSUPPORTED, "%s: num_queries %d > %d", fn, Q, kMaxQ);

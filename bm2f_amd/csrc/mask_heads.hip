@@ -25,17 +25,13 @@
 // 16-bit runs of bits are stored directly (the pyramid's 32/64/128-wide targets), other widths OR-ed in.
 // HBM-bound: the features are read once and the masks written once.
 #include "common.h"
+#include "device_util.h"
 
 #include <cstdint>
 
 namespace {
 
-using s4 = short __attribute__((ext_vector_type(4)));
-using s8 = short __attribute__((ext_vector_type(8)));
-using f16v = float __attribute__((ext_vector_type(16)));
-using bf8 = __bf16 __attribute__((ext_vector_type(8)));
-using h8 = _Float16 __attribute__((ext_vector_type(8)));
-using lds_s4 = __attribute__((address_space(3))) s4;
+using m2f::bf8, m2f::f16v, m2f::h8, m2f::s4, m2f::s8, m2f::tr_read;
 
 constexpr int kCols = 128;               // columns per workgroup
 constexpr int kKC = 32;                  // k per stage
@@ -43,27 +39,18 @@ constexpr int kFPitch = 2 * kCols + 32;  // LDS pitch of a feature k-row (elemen
 constexpr int kEPitch = kKC + 8;         // LDS pitch of an embed row (elements): 80 B
 constexpr int kThreads = 512;
 
+// device_util.h's conversions plus this file's 32x32x16 MFMA
 template <typename T> struct MhElt;
-template <> struct MhElt<__bf16> {
+template <> struct MhElt<__bf16> : m2f::Elt<__bf16> {
   __device__ static f16v mma(s8 a, s8 b, f16v c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, a), __builtin_bit_cast(bf8, b), c, 0, 0, 0);
   }
-  __device__ static float to_f(__bf16 x) { return static_cast<float>(x); }
-  __device__ static __bf16 from_f(float x) { return static_cast<__bf16>(x); }
 };
-template <> struct MhElt<_Float16> {
+template <> struct MhElt<_Float16> : m2f::Elt<_Float16> {
   __device__ static f16v mma(s8 a, s8 b, f16v c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
   }
-  __device__ static float to_f(_Float16 x) { return static_cast<float>(x); }
-  __device__ static _Float16 from_f(float x) { return static_cast<_Float16>(x); }
 };
-
-// Transposed 4x16 read: lane 4q+p of each 16-lane group passes the address of row q, columns 4p..4p+3 of
-// its block; lane i receives column i of the 4 rows (row q in element q).
-__device__ __forceinline__ s4 tr_read(const void* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(reinterpret_cast<uintptr_t>(p)));
-}
 
 struct MhArgs {
   const void* embed;    // (B, Q, C)

@@ -4,9 +4,11 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "device_util.h"
+
 namespace m2f_msda {
 
-using f4 = float __attribute__((ext_vector_type(4)));
+using m2f::f4;
 using f2 = float __attribute__((ext_vector_type(2)));
 
 // ------------------------------------------------------------------------------------------------
@@ -228,10 +230,5 @@ __device__ __forceinline__ QuadPoint quad_point_fl(int fh, int fw, float ly, flo
   k.lx = lx;
   return k;
 }
-
-__device__ __forceinline__ float pick4(const f4& v, int c) {
-  return c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w));
-}
-
 
 }  // namespace m2f_msda

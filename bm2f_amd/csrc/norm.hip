@@ -12,6 +12,7 @@
 // reduced by a second pass in a fixed order (deterministic).
 #include "bm2f.h"
 #include "common.h"
+#include "device_util.h"
 
 #include <hip/hip_runtime.h>
 
@@ -19,17 +20,11 @@
 
 namespace {
 
-using f4 = float __attribute__((ext_vector_type(4)));
+using m2f::f4, m2f::wave_sum;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kBwdBlocksMax = 1024;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 template <int NV>
 __global__ void __launch_bounds__(kThreads) add_ln_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b,

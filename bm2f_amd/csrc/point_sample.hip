@@ -24,6 +24,7 @@
 // in fp64 and writes the weighted cost: no atomics, bitwise repeatable, and no (B, Q, K) tensor in memory.
 #include "bm2f.h"
 #include "common.h"
+#include "device_util.h"
 
 #include <hip/hip_runtime.h>
 
@@ -40,19 +41,9 @@ constexpr int LOSS_PER_THREAD = 4;
 constexpr int LOSS_CHUNK = NT * LOSS_PER_THREAD;
 constexpr int kTgtU8 = 0, kTgtF32 = 1;
 
-__device__ __forceinline__ float load_logit(const void* __restrict__ p, int dtype, int64_t i) {
-  switch (dtype) {
-    case M2F_F16: return static_cast<float>(static_cast<const _Float16*>(p)[i]);
-    case M2F_BF16: return static_cast<float>(static_cast<const __bf16*>(p)[i]);
-    default: return static_cast<const float*>(p)[i];
-  }
-}
+using m2f::load_logit, m2f::wave_sum;
 
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
+// Not device_util.h's exp2 forms: expf / log1pf with an IEEE divide, which the mask criterion's parity bars need.
 __device__ __forceinline__ float sigmoid(float x) {  // accurate in both tails
   const float e = expf(-fabsf(x));
   const float r = 1.f / (1.f + e);
@@ -345,7 +336,7 @@ __global__ void __launch_bounds__(NT) loss_bwd_kernel(const void* __restrict__ m
 }
 
 int check_masks(const char* fn, const void* masks, int dtype, int64_t n_planes, int H, int W) {
-  if (dtype != M2F_F32 && dtype != M2F_F16 && dtype != M2F_BF16) return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
+  if (!m2f::is_float_dtype(dtype)) return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
   if (n_planes < 0 || H < 1 || W < 1) return m2f::fail(M2F_EINVAL, "%s: bad sizes", fn);
   if (static_cast<int64_t>(H) * W > INT32_MAX) return m2f::fail(M2F_EUNSUPPORTED, "%s: H * W > 2^31 - 1", fn);
   if (n_planes > 0 && !masks) return m2f::fail(M2F_EINVAL, "%s: null masks", fn);

@@ -21,6 +21,7 @@
 #include <cstdint>
 
 #include "bm2f.h"
+#include "device_util.h"  // load_logit: the typed load behind every ld(row, col)
 
 namespace m2f {
 
@@ -96,14 +97,6 @@ __device__ __forceinline__ AxisTaps axis_taps(int dst, bool two, float r1, int i
     a.t2 = Tap{dst, dst, 1.f, 0.f};
   }
   return a;
-}
-
-__device__ __forceinline__ float load_logit(const void* __restrict__ p, int dtype, int64_t i) {
-  switch (dtype) {
-    case M2F_F16: return static_cast<float>(static_cast<const _Float16*>(p)[i]);
-    case M2F_BF16: return static_cast<float>(static_cast<const __bf16*>(p)[i]);
-    default: return static_cast<const float*>(p)[i];
-  }
 }
 
 // The full-resolution logit from taps; ld(row, col) returns the fp32 source texel.

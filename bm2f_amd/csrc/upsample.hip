@@ -15,12 +15,13 @@
 // source pixel sums the <= 4 x 4 output pixels whose taps touch it, with the forward's weights.
 #include "bm2f.h"
 #include "common.h"
+#include "device_util.h"
 
 #include <hip/hip_runtime.h>
 
 namespace {
 
-using f4 = __attribute__((__vector_size__(4 * sizeof(float)))) float;
+using m2f::f4, m2f::pick4;
 
 struct Tap {
   int i0, i1;
@@ -76,10 +77,6 @@ __global__ void __launch_bounds__(256) up2x_add_fwd(const float* __restrict__ sr
 // contiguous source rows (sX == 1): the four output pixels of a thread read source columns 2t-1 .. 2t+2
 // (clamped) only, so each row is loaded once into a 4-value window (8 loads instead of 16); same taps,
 // same products and order as up2x_add_fwd (FMA contraction may differ: equal to fp32 rounding)
-__device__ __forceinline__ float pick4(const float (&v)[4], int j) {
-  return j == 0 ? v[0] : (j == 1 ? v[1] : (j == 2 ? v[2] : v[3]));
-}
-
 __global__ void __launch_bounds__(256) up2x_add_fwd_rows(const float* __restrict__ src, int64_t sN, int64_t sC,
                                                          int64_t sY, const float* __restrict__ lat,
                                                          float* __restrict__ out, int C, int h, int w, int64_t nvec) {

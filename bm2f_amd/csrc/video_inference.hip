@@ -149,8 +149,6 @@ __global__ void __launch_bounds__(256) feat_resize_pad_kernel(const void* __rest
                        ld(ty.i1, tx.i1));
 }
 
-bool bad_dtype(int dtype) { return dtype != M2F_F32 && dtype != M2F_F16 && dtype != M2F_BF16; }
-
 }  // namespace
 
 extern "C" int m2f_infer_video(const void* logits, int dtype, const int32_t* slot_query, const int32_t* num_sel,
@@ -159,7 +157,7 @@ extern "C" int m2f_infer_video(const void* logits, int dtype, const int32_t* slo
                                void* stream) {
   const char* fn = "m2f_infer_video";
   if (!logits || !slot_query || !out) return m2f::fail(M2F_EINVAL, "%s: null pointer", fn);
-  if (bad_dtype(dtype)) return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
+  if (!m2f::is_float_dtype(dtype)) return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
   if (num_queries <= 0 || num_slots <= 0 || num_frames <= 0 || in_h <= 0 || in_w <= 0 || pad_h <= 0 || pad_w <= 0 ||
       crop_h <= 0 || crop_w <= 0 || out_h <= 0 || out_w <= 0)
     return m2f::fail(M2F_EINVAL, "%s: sizes must be positive", fn);
@@ -199,7 +197,7 @@ extern "C" int m2f_feat_resize_pad(const void* feats, int dtype, int64_t planes,
                                    int pad_w, int out_h, int out_w, float* out, void* stream) {
   const char* fn = "m2f_feat_resize_pad";
   if (!feats || !out) return m2f::fail(M2F_EINVAL, "%s: null pointer", fn);
-  if (bad_dtype(dtype)) return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
+  if (!m2f::is_float_dtype(dtype)) return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
   if (planes <= 0 || src_h <= 0 || src_w <= 0 || pad_h <= 0 || pad_w <= 0 || out_h <= 0 || out_w <= 0)
     return m2f::fail(M2F_EINVAL, "%s: sizes must be positive", fn);
   if (src_h > pad_h || src_w > pad_w)

@@ -17,6 +17,7 @@
 // so the matrix is never written.
 #include "bm2f.h"
 #include "common.h"
+#include "device_util.h"
 
 #include <hip/hip_runtime.h>
 
@@ -25,35 +26,9 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
 
-// The log-space pair term of weaksup.hip (same forms, so the spatial and temporal losses round alike):
-// log(1 + exp(t)) for t <= 0 on the hardware exp2/log2
-__device__ __forceinline__ float softplus_neg(float t) {
-  return kLn2 * __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(t * kLog2e));
-}
-
-__device__ __forceinline__ float log_sigmoid(float x) { return fminf(x, 0.f) - softplus_neg(-fabsf(x)); }
-
-// s(a,b) = -(logsig(a) + logsig(b) + softplus(-(a+b)))
-__device__ __forceinline__ float pair_term(float a, float b) {
-  const float z = a + b;
-  return -(log_sigmoid(a) + log_sigmoid(b) + fmaxf(-z, 0.f) + softplus_neg(-fabsf(z)));
-}
-
-__device__ __forceinline__ float sigmoid_neg(float t) {  // sig(-t), accurate in both tails
-  const float e = __builtin_amdgcn_exp2f(-fabsf(t) * kLog2e);
-  const float r = __builtin_amdgcn_rcpf(1.f + e);
-  return t >= 0.f ? e * r : r;
-}
-
-// d s(a, b) / d a = sig(-(a+b)) - sig(-a)
-__device__ __forceinline__ float pair_grad(float a, float sna, float b) { return sigmoid_neg(a + b) - sna; }
-
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
+// the pair term and its gradient are device_util.h's, the very functions of the spatial loss (weaksup.hip)
+using m2f::log_sigmoid, m2f::pair_grad, m2f::pair_term, m2f::sigmoid_neg, m2f::wave_sum;
 
 // Matched row n of pair i, or -1 when the pair is dead: a negative / out-of-range target row, frame or
 // pixel (the packer marks invalid pairs with row -1) or a target that no query was matched to.
@@ -80,7 +55,8 @@ __global__ void __launch_bounds__(NT) temporal_fwd_kernel(const float* __restric
     const int n = pair_row(i, N, T, HW, row_of_target, n_targets, prow, pt, p0, p1);
     if (n >= 0) {
       const float* base = src + (static_cast<int64_t>(n) * T + pt[i]) * HW;
-      s = pair_term(base[p0[i]], base[HW + p1[i]]);
+      const float a = base[p0[i]], b = base[HW + p1[i]];
+      s = pair_term(a, log_sigmoid(a), b, log_sigmoid(b));
       live = 1;
     }
   }

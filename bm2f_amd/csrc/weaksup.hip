@@ -17,6 +17,7 @@
 // them in the reference.  Sums are per-tile partials (deterministic; reduced by the caller).
 #include "bm2f.h"
 #include "common.h"
+#include "device_util.h"
 
 #include <hip/hip_runtime.h>
 
@@ -37,34 +38,9 @@ __device__ __forceinline__ int tap_dx(int k) {
   return t % 3 - 1;
 }
 
-constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
-
-// log(1 + exp(t)) for t <= 0 on the raw hardware exp2/log2 (one v_exp_f32 + one v_log_f32; 1 + e lies in
-// [1, 2], so no denormal range fix-ups are needed)
-__device__ __forceinline__ float softplus_neg(float t) {
-  return kLn2 * __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(t * kLog2e));
-}
-
-__device__ __forceinline__ float log_sigmoid(float x) {  // F.logsigmoid: min(x,0) - log1p(exp(-|x|))
-  return fminf(x, 0.f) - softplus_neg(-fabsf(x));
-}
-
-// s(a,b) = -log(sig(a)sig(b) + sig(-a)sig(-b)) = -(logsig(a) + logsig(b) + softplus(-(a+b))): the
-// reference's log-space form (criterion.py:175-179, with logsig(-x) = logsig(x) - x) reduced to one
-// softplus per pair.  Pairs reaching outside the image are 0, as F.unfold's zero log-prob padding gives.
-__device__ __forceinline__ float pair_term(float a, float fa, float b, float fb) {
-  const float z = a + b;
-  return -(fa + fb + fmaxf(-z, 0.f) + softplus_neg(-fabsf(z)));
-}
-
-__device__ __forceinline__ float sigmoid_neg(float t) {  // sig(-t), accurate in both tails
-  const float e = __builtin_amdgcn_exp2f(-fabsf(t) * kLog2e);
-  const float r = __builtin_amdgcn_rcpf(1.f + e);
-  return t >= 0.f ? e * r : r;
-}
-
-// d s(a, b) / d a = sig(-(a+b)) - sig(-a)
-__device__ __forceinline__ float pair_grad(float a, float sna, float b) { return sigmoid_neg(a + b) - sna; }
+// the pair term and its gradient: device_util.h (one definition for the spatial and the temporal loss).
+// Pairs reaching outside the image are 0, as F.unfold's zero log-prob padding gives.
+using m2f::log_sigmoid, m2f::pair_grad, m2f::pair_term, m2f::sigmoid_neg, m2f::wave_sum;
 
 struct Tile {
   int ty0, tx0;
@@ -97,11 +73,6 @@ __device__ __forceinline__ unsigned neighbours_inside(int y, int x, int H, int W
 #pragma unroll
   for (int k = 0; k < 8; ++k) m |= (inside(y + tap_dy(k) * d, x + tap_dx(k) * d, H, W) ? 1u : 0u) << k;
   return m;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
 }
 
 // MODE 0: out[r, p] = sum_k bit_k(p) s_k(p)                          (image-shared similarity map)

@@ -19,16 +19,13 @@
 // fp32 I/O runs the same structure on the exact fp32 MFMA (16x16x4), whose one-element operands need no transposed
 // image.  DESIGN.md section 3 "Shifted-window attention" has the LDS / VGPR budget.
 #include "common.h"
+#include "device_util.h"
 
 #include <type_traits>
 
 namespace {
 
-using f4 = float __attribute__((ext_vector_type(4)));
-using s4 = short __attribute__((ext_vector_type(4)));
-using s8 = short __attribute__((ext_vector_type(8)));
-using h8 = _Float16 __attribute__((ext_vector_type(8)));
-using b8 = __bf16 __attribute__((ext_vector_type(8)));
+using m2f::bf8, m2f::f4, m2f::h8, m2f::s4, m2f::s8;
 using u4 = unsigned __attribute__((ext_vector_type(4)));
 using i4 = int __attribute__((ext_vector_type(4)));
 
@@ -36,8 +33,9 @@ constexpr int kD = 32;        // head dim of every Swin variant
 constexpr int kMinWs = 2, kMaxWs = 12;
 constexpr float kMasked = -100.0f;   // swin.py:438, not -inf: no row is ever fully masked
 
-template <typename T> struct Elt {
-  static constexpr bool k16 = sizeof(T) == 2;
+// device_util.h's element traits (k16) plus this file's LDS layout
+template <typename T> struct WinElt : m2f::Elt<T> {
+  using m2f::Elt<T>::k16;
   // row pitch (elements) of a row-major (token, 32) LDS image: 80 B (16-bit) / 144 B (fp32) rows keep the 16-byte
   // alignment of the staging stores and spread the 16 rows a fragment read touches over the banks
   static constexpr int KS = k16 ? 40 : 36;
@@ -57,14 +55,14 @@ __host__ __device__ inline int tiles_of(int ws) { return (ws * ws + 15) / 16; }
 // and puts the 16 rows of a read on distinct bank pairs
 __host__ __device__ inline int tpitch(int NP) { return NP + 4; }
 
-template <typename T> __host__ __device__ inline int rowmajor_elems(int NP) { return NP * Elt<T>::KS; }
-template <typename T> __host__ __device__ inline int trans_elems(int NP) { return Elt<T>::k16 ? kD * tpitch(NP) : 0; }
+template <typename T> __host__ __device__ inline int rowmajor_elems(int NP) { return NP * WinElt<T>::KS; }
+template <typename T> __host__ __device__ inline int trans_elems(int NP) { return WinElt<T>::k16 ? kD * tpitch(NP) : 0; }
 // bias table (floats), then token codes and pixel offsets (ints)
 __host__ __device__ inline int small_words(int ws, int NP) { return pad4((2 * ws - 1) * (2 * ws - 1)) + 2 * NP; }
 
 template <typename T> inline size_t fwd_lds_bytes(int ws) {
   const int NP = pad32(ws * ws);
-  return static_cast<size_t>(rowmajor_elems<T>(NP) + (Elt<T>::k16 ? trans_elems<T>(NP) : rowmajor_elems<T>(NP))) *
+  return static_cast<size_t>(rowmajor_elems<T>(NP) + (WinElt<T>::k16 ? trans_elems<T>(NP) : rowmajor_elems<T>(NP))) *
              sizeof(T) + static_cast<size_t>(small_words(ws, NP)) * 4;
 }
 // backward: phase A holds K, V (row-major), K^T and the per-wave table-gradient bins; phase B reuses the space for
@@ -99,12 +97,12 @@ template <typename T> __device__ __forceinline__ f4 mma_k32(s8 a, s8 b, f4 c) {
   if constexpr (std::is_same<T, _Float16>::value)
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
   else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8, a), __builtin_bit_cast(b8, b), c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8, a), __builtin_bit_cast(bf8, b), c, 0, 0, 0);
 }
 
 // c[4g + r][lane & 15] += sum_d a_row(lane & 15)[d] * b_row(lane & 15)[d]  (a's rows down, b's rows across)
 template <typename T> __device__ __forceinline__ f4 mma_d(const Frag<T>& a, const Frag<T>& b, f4 c) {
-  if constexpr (Elt<T>::k16) {
+  if constexpr (WinElt<T>::k16) {
     return mma_k32<T>(a.v, b.v, c);
   } else {
 #pragma unroll
@@ -120,7 +118,7 @@ template <typename T> __device__ __forceinline__ s8 pack8(f4 lo, f4 hi) {
             static_cast<_Float16>(hi[2]), static_cast<_Float16>(hi[3])};
     return __builtin_bit_cast(s8, p);
   } else {
-    b8 p = {static_cast<__bf16>(lo[0]), static_cast<__bf16>(lo[1]), static_cast<__bf16>(lo[2]),
+    bf8 p = {static_cast<__bf16>(lo[0]), static_cast<__bf16>(lo[1]), static_cast<__bf16>(lo[2]),
             static_cast<__bf16>(lo[3]), static_cast<__bf16>(hi[0]), static_cast<__bf16>(hi[1]),
             static_cast<__bf16>(hi[2]), static_cast<__bf16>(hi[3])};
     return __builtin_bit_cast(s8, p);
@@ -132,7 +130,7 @@ template <typename T> __device__ __forceinline__ s8 pack8(f4 lo, f4 hi) {
 // o1 = M[:, 16:32]^T X.  16-bit reads M^T (`img` = the transposed image, pitch `ld`); fp32 reads the row-major image.
 template <typename T, int NT>
 __device__ __forceinline__ void mma_tok(const T* img, int ld, const f4 (&X)[NT], f4& o0, f4& o1, int r16, int g) {
-  if constexpr (Elt<T>::k16) {
+  if constexpr (WinElt<T>::k16) {
 #pragma unroll
     for (int c = 0; c < (NT + 1) / 2; ++c) {
       const f4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -162,7 +160,7 @@ __device__ __forceinline__ void mma_tok(const T* img, int ld, const f4 (&X)[NT],
 
 // four consecutive channels of one token
 template <typename T> __device__ __forceinline__ void store4(T* p, f4 v) {
-  if constexpr (Elt<T>::k16) {
+  if constexpr (WinElt<T>::k16) {
     const s8 q = pack8<T>(v, v);
     *reinterpret_cast<s4*>(p) = __builtin_shufflevector(q, q, 0, 1, 2, 3);
   } else {
@@ -217,14 +215,14 @@ __device__ __forceinline__ void window_tables(const Geo& G, int wy, int wx, int 
 template <typename T>
 __device__ __forceinline__ void stage(const T* __restrict__ src, int64_t stride, const int* sPos, int N, int NP,
                                       T* rowmajor, T* trans) {
-  constexpr int EPC = Elt<T>::EPC, CPR = Elt<T>::CPR, KS = Elt<T>::KS;
+  constexpr int EPC = WinElt<T>::EPC, CPR = WinElt<T>::CPR, KS = WinElt<T>::KS;
   const int TS = tpitch(NP);
   for (int c = threadIdx.x; c < NP * CPR; c += blockDim.x) {
     const int j = c / CPR, ch = c - j * CPR;
     u4 v = {0u, 0u, 0u, 0u};
     if (j < N) v = *reinterpret_cast<const u4*>(src + sPos[j] * stride + ch * EPC);
     if (rowmajor) *reinterpret_cast<u4*>(rowmajor + j * KS + ch * EPC) = v;
-    if constexpr (Elt<T>::k16) {
+    if constexpr (WinElt<T>::k16) {
       if (trans) {
         const s8 e = __builtin_bit_cast(s8, v);
 #pragma unroll
@@ -255,11 +253,11 @@ __global__ __launch_bounds__(64 * NT) void wattn_fwd_kernel(const T* __restrict_
                                                             T* __restrict__ out, float* __restrict__ lse, Geo G,
                                                             float scale) {
   extern __shared__ __align__(16) unsigned char smem[];
-  constexpr int KS = Elt<T>::KS;
+  constexpr int KS = WinElt<T>::KS;
   const int ws = G.ws, N = ws * ws, NP = pad32(N), TW = 2 * ws - 1, C = G.nH * kD;
   T* sK = reinterpret_cast<T*>(smem);
   T* sV = sK + rowmajor_elems<T>(NP);   // 16-bit: V^T (32, tpitch); fp32: V row-major
-  float* sBias = reinterpret_cast<float*>(sV + (Elt<T>::k16 ? trans_elems<T>(NP) : rowmajor_elems<T>(NP)));
+  float* sBias = reinterpret_cast<float*>(sV + (WinElt<T>::k16 ? trans_elems<T>(NP) : rowmajor_elems<T>(NP)));
   int* sTok = reinterpret_cast<int*>(sBias + pad4(TW * TW));
   int* sPos = sTok + NP;
 
@@ -269,7 +267,7 @@ __global__ __launch_bounds__(64 * NT) void wattn_fwd_kernel(const T* __restrict_
   window_tables(G, k.wy, k.wx, k.h, table, sBias, sTok, sPos, NP);
   __syncthreads();
   stage<T>(base + C, 3 * C, sPos, N, NP, sK, nullptr);
-  if constexpr (Elt<T>::k16) stage<T>(base + 2 * C, 3 * C, sPos, N, NP, nullptr, sV);
+  if constexpr (WinElt<T>::k16) stage<T>(base + 2 * C, 3 * C, sPos, N, NP, nullptr, sV);
   else stage<T>(base + 2 * C, 3 * C, sPos, N, NP, sV, nullptr);
   __syncthreads();
 
@@ -312,7 +310,7 @@ __global__ __launch_bounds__(64 * NT) void wattn_fwd_kernel(const T* __restrict_
     }
   l = wave_sum4(l);
   f4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
-  mma_tok<T, NT>(sV, Elt<T>::k16 ? tpitch(NP) : KS, S, o0, o1, r16, g);
+  mma_tok<T, NT>(sV, WinElt<T>::k16 ? tpitch(NP) : KS, S, o0, o1, r16, g);
   if (valid) {   // tail query rows are not stored
     const float inv = 1.f / l;
     T* o = out + (img + posq) * C + k.h * kD + 4 * g;
@@ -336,8 +334,8 @@ __global__ __launch_bounds__(64 * NT) void wattn_bwd_kernel(const T* __restrict_
                                                             T* __restrict__ dqkv, float* __restrict__ part, Geo G,
                                                             float scale) {
   extern __shared__ __align__(16) unsigned char smem[];
-  constexpr int KS = Elt<T>::KS;
-  constexpr bool k16 = Elt<T>::k16;
+  constexpr int KS = WinElt<T>::KS;
+  constexpr bool k16 = WinElt<T>::k16;
   const int ws = G.ws, N = ws * ws, NP = pad32(N), TW = 2 * ws - 1, TB = TW * TW, TBp = pad4(TB), C = G.nH * kD;
   const int TS = tpitch(NP), RM = rowmajor_elems<T>(NP), TR = trans_elems<T>(NP);
   // phase A                      phase B

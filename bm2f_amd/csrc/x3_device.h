@@ -4,11 +4,11 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "device_util.h"
+
 namespace m2f_x3 {
 
-using f4 = float __attribute__((ext_vector_type(4)));
-using f16v = float __attribute__((ext_vector_type(16)));
-using bf8 = __bf16 __attribute__((ext_vector_type(8)));
+using m2f::bf8, m2f::f16v, m2f::f4, m2f::xcd_remap;
 using bf4 = __bf16 __attribute__((ext_vector_type(4)));
 
 constexpr int kBK = 16;  // k per stage = one 32x32x16 MFMA step
@@ -35,14 +35,8 @@ __device__ __forceinline__ f16v mfma_x3(const bf8 (&a)[3], bf8 bh, bf8 bm, bf8 b
   return mfma(a[0], bh, c);  // ah.bh
 }
 
-// bijective XCD-aware remap: consecutive logical ids land on the same XCD (blocks id, id+8, ... share one)
-__device__ __forceinline__ int xcd_remap(int id, int nwg) {
-  const int q = nwg / 8, r = nwg % 8, xcd = id % 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + id / 8;
-}
-
-// grouped XCD remap: blocks are dealt to XCDs round-robin (b % 8), so consecutive block ids cover one group
-// of 8*G logical tiles at a time (the chip streams one contiguous region, spread over all HBM channels) and
+// grouped XCD remap (the plain one is device_util.h's xcd_remap): blocks are dealt to XCDs round-robin
+// (b % 8), so consecutive block ids cover one group of 8*G logical tiles at a time (the chip streams one contiguous region, spread over all HBM channels) and
 // XCD b % 8 gets the contiguous run of G tiles inside it (neighbouring tiles share one L2).  Bijective:
 // the partial last group keeps identity order.
 __device__ __forceinline__ int xcd_group_remap(int b, int nwg, int G) {

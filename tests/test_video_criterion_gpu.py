@@ -110,6 +110,29 @@ def test_temporal_kernel_vs_fp64(device):
     assert torch.equal(first, xd.grad) and torch.equal(total, total2)   # no atomics: bitwise repeatable
 
 
+def test_temporal_term_equals_spatial_term(device):
+    """The temporal and the spatial loss evaluate one pair_term (csrc/device_util.h): on the same two logits they
+    give the same fp32 value.  Both frames of a clip hold one plane, so the temporal pair (pixel (y, x) of frame 0,
+    pixel (y, x + 1) of frame 1) is the spatial pair of (y, x) with its right-hand neighbour (tap 4, dilation 1).
+    One pair per launch: the block reduction then adds only zeros to the term, so the sum is the term itself (a
+    -0 term sums to +0: compared as values) and the comparison is exact (same expression, same compile flags: no
+    tolerance to grant)."""
+    H, W = 5, 9
+    g = torch.Generator().manual_seed(3)
+    plane = torch.randn(H, W, generator=g) * 4
+    plane[0, :4] = torch.tensor([40.0, 40.0, -40.0, -40.0])   # saturated: ++, +-, --
+    plane[1, :3] = torch.tensor([0.0, 0.0, 1e-3])
+    x = plane.expand(1, 2, H, W).contiguous().to(device)
+    spatial = weaksup.pairwise_planes(x[0, :1].contiguous(), 1)[0, 4].cpu()
+    rot = torch.zeros(1, dtype=torch.int32, device=device)
+    for y, xx in [(0, 0), (0, 1), (0, 2), (1, 0), (1, 1), (2, 3), (4, 7)]:
+        cur, nxt = torch.tensor([[xx, y]], dtype=torch.int32), torch.tensor([[xx + 1, y]], dtype=torch.int32)
+        pk = weaksup.pack_temporal_pairs([[[(cur, nxt)]]], 2, H, W, device)
+        total, count = weaksup.temporal_pair_sum(x, rot, pk)
+        print(f"pair ({y}, {xx}): temporal {float(total):.9g} spatial {float(spatial[y, xx]):.9g}")
+        assert int(count) == 1 and float(total) == float(spatial[y, xx]) and float(total) >= 0.0
+
+
 def test_temporal_kernel_no_pairs(device):
     T, H, W = 3, 17, 45
     e = torch.zeros((0, 2), dtype=torch.int64)
