@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
 #include "bm2f.h"
 
@@ -41,6 +42,57 @@ inline unsigned ceil_div(int64_t a, int64_t b) { return static_cast<unsigned>((a
 
 // one of the three floating-point element types of the C ABI
 inline bool is_float_dtype(int dtype) { return dtype == M2F_F32 || dtype == M2F_F16 || dtype == M2F_BF16; }
+
+// Runtime value -> kernel template argument, once for every entry point.  f is a generic lambda that launches;
+// it returns nothing and reports through what it captures.  The dispatch_* that can miss return false without
+// calling f, and the caller answers with its own message.
+template <typename T>
+struct Tag { using type = T; };
+
+template <typename F>
+inline bool dispatch_half(int dtype, F&& f) {
+  if (dtype == M2F_BF16) f(Tag<__bf16>{});
+  else if (dtype == M2F_F16) f(Tag<_Float16>{});
+  else return false;
+  return true;
+}
+
+template <typename F>
+inline bool dispatch_float(int dtype, F&& f) {
+  if (dtype == M2F_F32) f(Tag<float>{});
+  else return dispatch_half(dtype, f);
+  return true;
+}
+
+template <typename F>
+inline void dispatch_bool(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// K = v for v in Ks..., else no call
+template <int... Ks, typename F>
+inline bool dispatch_one_of(int v, F&& f) {
+  return ((v == Ks && (f(std::integral_constant<int, Ks>{}), true)) || ...);
+}
+
+// K = v for LO <= v < HI; every other v takes HI, as the `default:` of a switch over a level count did
+template <int LO, int HI, typename F>
+inline void dispatch_int(int v, F&& f) {
+  if constexpr (LO < HI) {
+    if (v == LO) return f(std::integral_constant<int, LO>{});
+    return dispatch_int<LO + 1, HI>(v, f);
+  } else {
+    f(std::integral_constant<int, HI>{});
+  }
+}
+
+// nb workgroups as a 1-D grid: a count that the grid cannot hold is refused in fn's name
+inline int grid_1d(int64_t nb, const char* fn, unsigned* grid) {
+  if (nb > 0x7fffffff) return fail(M2F_EUNSUPPORTED, "%s: too many workgroups", fn);
+  *grid = static_cast<unsigned>(nb);
+  return M2F_OK;
+}
 
 // Explicit tuning options (m2f_set_option, include/bm2f.h): geometry and engine overrides for tests and
 // tools.  The library never reads the environment; an unset option means the built-in default.  Every

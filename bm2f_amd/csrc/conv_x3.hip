@@ -624,18 +624,20 @@ int conv_impl(const char* fn, const void* I, int i_dtype, int i_nhwc, const floa
     if (nblk > 0x7fffffff) return m2f::fail(M2F_EUNSUPPORTED, "%s: too many tiles", fn);
     x3_conv_kernel<9><<<static_cast<unsigned>(nblk), 256, 0, st>>>(static_cast<const float*>(I), Ca, H, W, Bs, NP,
                                                                     bias, static_cast<float*>(O), Nn);
-  } else if (mode == 0) {
-    if (i_dtype == M2F_F32) launch_1x1<float, float, false, false>(I, Ca, H, W, Bs, NP, bias, O, Nn, N, st);
-    else if (i_dtype == M2F_F16 && i_nhwc) launch_1x1<_Float16, float, true, false>(I, Ca, H, W, Bs, NP, bias, O, Nn, N, st);
-    else if (i_dtype == M2F_F16) launch_1x1<_Float16, float, false, false>(I, Ca, H, W, Bs, NP, bias, O, Nn, N, st);
-    else if (i_nhwc) launch_1x1<__bf16, float, true, false>(I, Ca, H, W, Bs, NP, bias, O, Nn, N, st);
-    else launch_1x1<__bf16, float, false, false>(I, Ca, H, W, Bs, NP, bias, O, Nn, N, st);
+  } else if (!i16 && !o16) {   // either mode: all fp32, NCHW (io_ok above)
+    launch_1x1<float, float, false, false>(I, Ca, H, W, Bs, NP, bias, O, Nn, N, st);
+  } else if (mode == 0) {      // the 16-bit operand in either layout
+    m2f::dispatch_half(i_dtype, [&](auto t) {
+      m2f::dispatch_bool(i_nhwc != 0, [&](auto nhwc) {
+        launch_1x1<typename decltype(t)::type, float, nhwc.value, false>(I, Ca, H, W, Bs, NP, bias, O, Nn, N, st);
+      });
+    });
   } else {
-    if (o_dtype == M2F_F32) launch_1x1<float, float, false, false>(I, Ca, H, W, Bs, NP, bias, O, Nn, N, st);
-    else if (o_dtype == M2F_F16 && o_nhwc) launch_1x1<float, _Float16, false, true>(I, Ca, H, W, Bs, NP, bias, O, Nn, N, st);
-    else if (o_dtype == M2F_F16) launch_1x1<float, _Float16, false, false>(I, Ca, H, W, Bs, NP, bias, O, Nn, N, st);
-    else if (o_nhwc) launch_1x1<float, __bf16, false, true>(I, Ca, H, W, Bs, NP, bias, O, Nn, N, st);
-    else launch_1x1<float, __bf16, false, false>(I, Ca, H, W, Bs, NP, bias, O, Nn, N, st);
+    m2f::dispatch_half(o_dtype, [&](auto t) {
+      m2f::dispatch_bool(o_nhwc != 0, [&](auto nhwc) {
+        launch_1x1<float, typename decltype(t)::type, false, nhwc.value>(I, Ca, H, W, Bs, NP, bias, O, Nn, N, st);
+      });
+    });
   }
   return m2f::check_launch(fn);
 }
@@ -672,11 +674,12 @@ int wgrad_impl(const char* fn, const float* dO, const void* I, int i_dtype, int 
   const int tiles = ((T * Ci + 127) / 128) * ((Co + 255) / 256);
   const unsigned grid = static_cast<unsigned>(p.splits * tiles);
   float* bs = dbias ? bslab : nullptr;
-  if (i_dtype == M2F_F32) launch_wgrad<float, false>(T, grid, dO, I, N, Co, Ci, H, W, p.rows, slab, bs, st);
-  else if (i_dtype == M2F_F16 && i_nhwc) launch_wgrad<_Float16, true>(T, grid, dO, I, N, Co, Ci, H, W, p.rows, slab, bs, st);
-  else if (i_dtype == M2F_F16) launch_wgrad<_Float16, false>(T, grid, dO, I, N, Co, Ci, H, W, p.rows, slab, bs, st);
-  else if (i_nhwc) launch_wgrad<__bf16, true>(T, grid, dO, I, N, Co, Ci, H, W, p.rows, slab, bs, st);
-  else launch_wgrad<__bf16, false>(T, grid, dO, I, N, Co, Ci, H, W, p.rows, slab, bs, st);
+  if (!i16) launch_wgrad<float, false>(T, grid, dO, I, N, Co, Ci, H, W, p.rows, slab, bs, st);
+  m2f::dispatch_half(i_dtype, [&](auto t) {
+    m2f::dispatch_bool(i_nhwc != 0, [&](auto nhwc) {
+      launch_wgrad<typename decltype(t)::type, nhwc.value>(T, grid, dO, I, N, Co, Ci, H, W, p.rows, slab, bs, st);
+    });
+  });
   if ((rc = m2f::check_launch(fn))) return rc;
   // the slab sum lands as [(tap, ci)][co]; the caller permutes it to [co][ci][tap]
   const int64_t n = static_cast<int64_t>(T) * Ci * Co;

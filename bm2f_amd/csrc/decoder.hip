@@ -1306,14 +1306,10 @@ int mattn_fwd_impl(const char* fn, const void* q, const void* k, const void* v, 
   const T* kk = static_cast<const T*>(k);
   const T* vv = static_cast<const T*>(v);
   T* oo = static_cast<T*>(out);
-  if (tpw <= 1)
-    mattn_fwd_kernel<T, 1><<<grid, 256, 0, st>>>(qq, kk, vv, bits, Lq, Lk, H, qs, kvs, nw, sl2, chunk, oo, lse2, ws_o, ws_ml, xm);
-  else if (tpw <= 2)
-    mattn_fwd_kernel<T, 2><<<grid, 256, 0, st>>>(qq, kk, vv, bits, Lq, Lk, H, qs, kvs, nw, sl2, chunk, oo, lse2, ws_o, ws_ml, xm);
-  else if (tpw <= 4)
-    mattn_fwd_kernel<T, 4><<<grid, 256, 0, st>>>(qq, kk, vv, bits, Lq, Lk, H, qs, kvs, nw, sl2, chunk, oo, lse2, ws_o, ws_ml, xm);
-  else
-    mattn_fwd_kernel<T, 8><<<grid, 256, 0, st>>>(qq, kk, vv, bits, Lq, Lk, H, qs, kvs, nw, sl2, chunk, oo, lse2, ws_o, ws_ml, xm);
+  m2f::dispatch_one_of<1, 2, 4, 8>(tpw <= 1 ? 1 : tpw <= 2 ? 2 : tpw <= 4 ? 4 : 8, [&](auto tp) {
+    mattn_fwd_kernel<T, tp.value><<<grid, 256, 0, st>>>(qq, kk, vv, bits, Lq, Lk, H, qs, kvs, nw, sl2, chunk, oo, lse2,
+                                                        ws_o, ws_ml, xm);
+  });
   int rc = m2f::check_launch(fn);
   if (rc || nch == 1) return rc;
   // option mattn_combine: 0 = one thread per (row, 4 channels), 1 = one wave per row; default: the wave form from 16
@@ -1404,12 +1400,13 @@ extern "C" int m2f_attn_mask_bits(const void* logits, int dtype, int batch, int 
                                   void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
   const char* fn = "m2f_attn_mask_bits";
-  switch (dtype) {
-    case M2F_F32: return attn_mask_impl<float>(fn, logits, batch, num_queries, frames, in_h, in_w, out_h, out_w, row_fix, bits, nwords, st);
-    case M2F_BF16: return attn_mask_impl<__bf16>(fn, logits, batch, num_queries, frames, in_h, in_w, out_h, out_w, row_fix, bits, nwords, st);
-    case M2F_F16: return attn_mask_impl<_Float16>(fn, logits, batch, num_queries, frames, in_h, in_w, out_h, out_w, row_fix, bits, nwords, st);
-    default: return m2f::fail(M2F_EUNSUPPORTED, "m2f_attn_mask_bits: dtype %d", dtype);
-  }
+  int rc = M2F_OK;
+  if (!m2f::dispatch_float(dtype, [&](auto t) {
+        rc = attn_mask_impl<typename decltype(t)::type>(fn, logits, batch, num_queries, frames, in_h, in_w, out_h, out_w,
+                                                        row_fix, bits, nwords, st);
+      }))
+    return m2f::fail(M2F_EUNSUPPORTED, "m2f_attn_mask_bits: dtype %d", dtype);
+  return rc;
 }
 
 extern "C" int m2f_masked_attn_plan(int batch, int num_queries, int num_keys, int num_heads, int* chunk_len,
@@ -1433,12 +1430,13 @@ extern "C" int m2f_masked_attn_fwd(int dtype, const void* q, const void* k, cons
   float* ws = static_cast<float*>(workspace);
   const size_t wb = workspace_bytes > 0 ? static_cast<size_t>(workspace_bytes) : 0;
   const char* fn = "m2f_masked_attn_fwd";
-  switch (dtype) {
-    case M2F_F32: return mattn_fwd_impl<float>(fn, q, k, v, bits, batch, num_queries, num_keys, num_heads, head_dim, q_row_stride, kv_row_stride, mask_words, scale, out, lse, ws, wb, st);
-    case M2F_BF16: return mattn_fwd_impl<__bf16>(fn, q, k, v, bits, batch, num_queries, num_keys, num_heads, head_dim, q_row_stride, kv_row_stride, mask_words, scale, out, lse, ws, wb, st);
-    case M2F_F16: return mattn_fwd_impl<_Float16>(fn, q, k, v, bits, batch, num_queries, num_keys, num_heads, head_dim, q_row_stride, kv_row_stride, mask_words, scale, out, lse, ws, wb, st);
-    default: return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
-  }
+  int rc = M2F_OK;
+  if (!m2f::dispatch_float(dtype, [&](auto t) {
+        rc = mattn_fwd_impl<typename decltype(t)::type>(fn, q, k, v, bits, batch, num_queries, num_keys, num_heads, head_dim,
+                                                        q_row_stride, kv_row_stride, mask_words, scale, out, lse, ws, wb, st);
+      }))
+    return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
+  return rc;
 }
 
 extern "C" int m2f_masked_attn_bwd(int dtype, const void* q, const void* k, const void* v, const uint32_t* bits,
@@ -1450,10 +1448,12 @@ extern "C" int m2f_masked_attn_bwd(int dtype, const void* q, const void* k, cons
   float* ws = static_cast<float*>(workspace);
   const size_t wb = workspace_bytes > 0 ? static_cast<size_t>(workspace_bytes) : 0;
   const char* fn = "m2f_masked_attn_bwd";
-  switch (dtype) {
-    case M2F_F32: return mattn_bwd_impl<float>(fn, q, k, v, bits, out, grad_out, lse, batch, num_queries, num_keys, num_heads, head_dim, q_row_stride, kv_row_stride, mask_words, scale, grad_q, grad_k, grad_v, ws, wb, st);
-    case M2F_BF16: return mattn_bwd_impl<__bf16>(fn, q, k, v, bits, out, grad_out, lse, batch, num_queries, num_keys, num_heads, head_dim, q_row_stride, kv_row_stride, mask_words, scale, grad_q, grad_k, grad_v, ws, wb, st);
-    case M2F_F16: return mattn_bwd_impl<_Float16>(fn, q, k, v, bits, out, grad_out, lse, batch, num_queries, num_keys, num_heads, head_dim, q_row_stride, kv_row_stride, mask_words, scale, grad_q, grad_k, grad_v, ws, wb, st);
-    default: return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
-  }
+  int rc = M2F_OK;
+  if (!m2f::dispatch_float(dtype, [&](auto t) {
+        rc = mattn_bwd_impl<typename decltype(t)::type>(fn, q, k, v, bits, out, grad_out, lse, batch, num_queries, num_keys,
+                                                        num_heads, head_dim, q_row_stride, kv_row_stride, mask_words, scale,
+                                                        grad_q, grad_k, grad_v, ws, wb, st);
+      }))
+    return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
+  return rc;
 }

@@ -57,16 +57,13 @@ extern "C" int m2f_bias_act_nchw(void* x, const void* residual, const float* bia
   if (nvec == 0) return m2f::ok();
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned grid = m2f::ceil_div(nvec, 256);
-#define M2F_BA(T, V, L) bias_act_kernel<T, V, L><<<grid, 256, 0, st>>>(static_cast<T*>(x), static_cast<const T*>(residual), \
-                                                                      bias, nvec, C, static_cast<int>(HW / V))
-  if (dtype == M2F_BF16) {
-    if (channels_last) M2F_BA(__bf16, 8, true); else M2F_BA(__bf16, 8, false);
-  } else if (dtype == M2F_F16) {
-    if (channels_last) M2F_BA(_Float16, 8, true); else M2F_BA(_Float16, 8, false);
-  } else {
-    if (channels_last) M2F_BA(float, 4, true); else M2F_BA(float, 4, false);
-  }
-#undef M2F_BA
+  m2f::dispatch_float(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    m2f::dispatch_bool(channels_last != 0, [&](auto nhwc) {
+      bias_act_kernel<T, 16 / sizeof(T), nhwc.value><<<grid, 256, 0, st>>>(
+          static_cast<T*>(x), static_cast<const T*>(residual), bias, nvec, C, static_cast<int>(HW / V));
+    });
+  });
   return m2f::check_launch(fn);
 }
 
@@ -129,15 +126,11 @@ extern "C" int m2f_relu_bwd_sum(const void* const* grads, int ngrads, const void
   if (nvec == 0) return m2f::ok();
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned grid = m2f::ceil_div(nvec, 256);
-  if (dtype == M2F_BF16)
-    relu_bwd_sum_kernel<__bf16, 8><<<grid, 256, 0, st>>>(gs, ngrads, static_cast<const __bf16*>(y),
-                                                         static_cast<__bf16*>(out), nvec);
-  else if (dtype == M2F_F16)
-    relu_bwd_sum_kernel<_Float16, 8><<<grid, 256, 0, st>>>(gs, ngrads, static_cast<const _Float16*>(y),
-                                                           static_cast<_Float16*>(out), nvec);
-  else
-    relu_bwd_sum_kernel<float, 4><<<grid, 256, 0, st>>>(gs, ngrads, static_cast<const float*>(y),
-                                                        static_cast<float*>(out), nvec);
+  m2f::dispatch_float(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    relu_bwd_sum_kernel<T, 16 / sizeof(T)><<<grid, 256, 0, st>>>(gs, ngrads, static_cast<const T*>(y),
+                                                                static_cast<T*>(out), nvec);
+  });
   return m2f::check_launch(fn);
 }
 
@@ -196,9 +189,9 @@ extern "C" int m2f_sum_to_f32(const void* const* srcs, int k, int64_t n, int dty
   if (nvec == 0) return m2f::ok();
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned grid = m2f::ceil_div(nvec, 256);
-  if (dtype == M2F_BF16) sum_to_f32_kernel<__bf16, 8><<<grid, 256, 0, st>>>(ts, k, out, nvec);
-  else if (dtype == M2F_F16) sum_to_f32_kernel<_Float16, 8><<<grid, 256, 0, st>>>(ts, k, out, nvec);
-  else sum_to_f32_kernel<float, 8><<<grid, 256, 0, st>>>(ts, k, out, nvec);
+  m2f::dispatch_float(dtype, [&](auto t) {
+    sum_to_f32_kernel<typename decltype(t)::type, 8><<<grid, 256, 0, st>>>(ts, k, out, nvec);
+  });
   return m2f::check_launch(fn);
 }
 
@@ -419,15 +412,15 @@ extern "C" int m2f_maxpool3s2_nhwc(int backward, const void* src, void* dst, uin
   if (total8 == 0) return m2f::ok();
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned grid = m2f::ceil_div(total8, 256);
-#define M2F_MPN(T)                                                                                                     \
-  if (backward)                                                                                                        \
-    maxpool3s2_bwd_nhwc<T><<<grid, 256, 0, st>>>(static_cast<const T*>(src), window, static_cast<T*>(dst), H, W, OH,   \
-                                                 OW, C, total8);                                                       \
-  else                                                                                                                 \
-    maxpool3s2_fwd_nhwc<T><<<grid, 256, 0, st>>>(static_cast<const T*>(src), static_cast<T*>(dst), window, H, W, OH,   \
-                                                 OW, C, total8);
-  if (dtype == M2F_BF16) { M2F_MPN(__bf16) } else { M2F_MPN(_Float16) }
-#undef M2F_MPN
+  m2f::dispatch_half(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if (backward)
+      maxpool3s2_bwd_nhwc<T><<<grid, 256, 0, st>>>(static_cast<const T*>(src), window, static_cast<T*>(dst), H, W, OH,
+                                                   OW, C, total8);
+    else
+      maxpool3s2_fwd_nhwc<T><<<grid, 256, 0, st>>>(static_cast<const T*>(src), static_cast<T*>(dst), window, H, W, OH,
+                                                   OW, C, total8);
+  });
   return m2f::check_launch(fn);
 }
 
@@ -440,16 +433,10 @@ extern "C" int m2f_maxpool3s2_fwd(const void* x, void* y, uint8_t* window, int64
   if (total == 0) return m2f::ok();
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned grid = m2f::ceil_div(total, 256);
-  if (dtype == M2F_BF16)
-    maxpool3s2_fwd<__bf16><<<grid, 256, 0, st>>>(static_cast<const __bf16*>(x), static_cast<__bf16*>(y), window, H,
-                                                 W, OH, OW, total);
-  else if (dtype == M2F_F16)
-    maxpool3s2_fwd<_Float16><<<grid, 256, 0, st>>>(static_cast<const _Float16*>(x), static_cast<_Float16*>(y), window,
-                                                   H, W, OH, OW, total);
-  else if (dtype == M2F_F32)
-    maxpool3s2_fwd<float><<<grid, 256, 0, st>>>(static_cast<const float*>(x), static_cast<float*>(y), window, H, W,
-                                                OH, OW, total);
-  else
+  if (!m2f::dispatch_float(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        maxpool3s2_fwd<T><<<grid, 256, 0, st>>>(static_cast<const T*>(x), static_cast<T*>(y), window, H, W, OH, OW, total);
+      }))
     return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
   return m2f::check_launch(fn);
 }
@@ -466,28 +453,19 @@ extern "C" int m2f_maxpool3s2_bwd(const void* grad_y, const uint8_t* window, voi
   if (W % 8 == 0 && m2f::aligned(grad_x, 16) && m2f::is_float_dtype(dtype)) {
     const int64_t total8 = total / 8;
     const unsigned g8 = m2f::ceil_div(total8, 256);
-    if (dtype == M2F_BF16)
-      maxpool3s2_bwd8<__bf16><<<g8, 256, 0, st>>>(static_cast<const __bf16*>(grad_y), window,
-                                                   static_cast<__bf16*>(grad_x), H, W, OH, OW, total8);
-    else if (dtype == M2F_F16)
-      maxpool3s2_bwd8<_Float16><<<g8, 256, 0, st>>>(static_cast<const _Float16*>(grad_y), window,
-                                                     static_cast<_Float16*>(grad_x), H, W, OH, OW, total8);
-    else
-      maxpool3s2_bwd8<float><<<g8, 256, 0, st>>>(static_cast<const float*>(grad_y), window,
-                                                  static_cast<float*>(grad_x), H, W, OH, OW, total8);
+    m2f::dispatch_float(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      maxpool3s2_bwd8<T><<<g8, 256, 0, st>>>(static_cast<const T*>(grad_y), window, static_cast<T*>(grad_x), H, W, OH,
+                                             OW, total8);
+    });
     return m2f::check_launch(fn);
   }
   const unsigned grid = m2f::ceil_div(total, 256);
-  if (dtype == M2F_BF16)
-    maxpool3s2_bwd<__bf16><<<grid, 256, 0, st>>>(static_cast<const __bf16*>(grad_y), window,
-                                                 static_cast<__bf16*>(grad_x), H, W, OH, OW, total);
-  else if (dtype == M2F_F16)
-    maxpool3s2_bwd<_Float16><<<grid, 256, 0, st>>>(static_cast<const _Float16*>(grad_y), window,
-                                                   static_cast<_Float16*>(grad_x), H, W, OH, OW, total);
-  else if (dtype == M2F_F32)
-    maxpool3s2_bwd<float><<<grid, 256, 0, st>>>(static_cast<const float*>(grad_y), window,
-                                                static_cast<float*>(grad_x), H, W, OH, OW, total);
-  else
+  if (!m2f::dispatch_float(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        maxpool3s2_bwd<T><<<grid, 256, 0, st>>>(static_cast<const T*>(grad_y), window, static_cast<T*>(grad_x), H, W, OH,
+                                                OW, total);
+      }))
     return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
   return m2f::check_launch(fn);
 }
@@ -644,16 +622,14 @@ extern "C" int m2f_colsum(int dtype, const void* src, int64_t rows, int cols, fl
   // 8-column vectors when every row starts 16-byte aligned and cols % 8 == 0, else one column per thread
   const int esz = dtype == M2F_F32 ? 4 : 2;
   const bool vec = cols % 8 == 0 && m2f::aligned(src, 16) && (static_cast<int64_t>(cols) * esz) % 16 == 0;
-#define M2F_COLSUM(T)                                                                                                   \
-  (vec ? colsum_part_kernel<T, 8><<<grid, 256, 0, st>>>(static_cast<const T*>(src), rows, cols, rows_per, workspace)   \
-       : colsum_part_kernel<T, 1><<<grid, 256, 0, st>>>(static_cast<const T*>(src), rows, cols, rows_per, workspace))
-  switch (dtype) {
-    case M2F_F32: M2F_COLSUM(float); break;
-    case M2F_F16: M2F_COLSUM(_Float16); break;
-    case M2F_BF16: M2F_COLSUM(__bf16); break;
-    default: return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
-  }
-#undef M2F_COLSUM
+  if (!m2f::dispatch_float(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        m2f::dispatch_bool(vec, [&](auto v8) {
+          colsum_part_kernel<T, v8.value ? 8 : 1><<<grid, 256, 0, st>>>(static_cast<const T*>(src), rows, cols, rows_per,
+                                                                       workspace);
+        });
+      }))
+    return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, dtype);
   colsum_final_kernel<<<(cols + 63) / 64, 256, 0, st>>>(workspace, static_cast<int>(chunks), cols, out);
   return m2f::check_launch(fn);
 }

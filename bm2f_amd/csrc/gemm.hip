@@ -207,17 +207,11 @@ int launch_nt(int epi, const float* A, int64_t lda, const float* B, int64_t ldb,
   const int64_t nwg = static_cast<int64_t>((M + BM - 1) / BM) * ((N + BN - 1) / BN);
   if (nwg > 0x7fffffff) return m2f::fail(M2F_EUNSUPPORTED, "m2f_gemm_f32_nt: too many tiles");
   const dim3 grid(static_cast<unsigned>(nwg)), block(64 * WM * WN);
-#define M2F_NT(E) gemm_nt_kernel<BM, BN, WM, WN, E, DEPTH><<<grid, block, 0, st>>>(A, lda, B, ldb, bias, mask, ldm, C, ldc, M, N, K)
-  switch (epi) {
-    case kNone: M2F_NT(kNone); break;
-    case kBias: M2F_NT(kBias); break;
-    case kRelu: M2F_NT(kRelu); break;
-    case kBias | kRelu: M2F_NT(kBias | kRelu); break;
-    case kMask: M2F_NT(kMask); break;
-    case kBias | kMask: M2F_NT(kBias | kMask); break;
-    default: return m2f::fail(M2F_EINVAL, "m2f_gemm_f32_nt: epilogue %d", epi);
-  }
-#undef M2F_NT
+  if (!m2f::dispatch_one_of<kNone, kBias, kRelu, kBias | kRelu, kMask, kBias | kMask>(epi, [&](auto e) {
+        gemm_nt_kernel<BM, BN, WM, WN, e.value, DEPTH><<<grid, block, 0, st>>>(A, lda, B, ldb, bias, mask, ldm, C, ldc, M,
+                                                                              N, K);
+      }))
+    return m2f::fail(M2F_EINVAL, "m2f_gemm_f32_nt: epilogue %d", epi);
   return m2f::check_launch("m2f_gemm_f32_nt");
 }
 

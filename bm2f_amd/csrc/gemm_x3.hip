@@ -316,27 +316,14 @@ int launch_nt(int epi, const float* A, int64_t lda, const __bf16* Bs, int NP, co
   const int64_t nwg = static_cast<int64_t>((M + BM - 1) / BM) * ((N + BN - 1) / BN);
   if (nwg > 0x7fffffff) return m2f::fail(M2F_EUNSUPPORTED, "m2f_gemm_f32x3_nt: too many tiles");
   const dim3 grid(static_cast<unsigned>(nwg)), block(64 * NW);
-#define M2F_X3NT(E)                                                                                            \
-  (K % kBK == 0 ? x3_nt_kernel<BN, NW, E, true><<<grid, block, 0, st>>>(A, lda, Bs, NP, bias, mask, ldm, D1, D2, ldd, \
-                                                                       dper, bits, C, ldc, M, N, K)               \
-                : x3_nt_kernel<BN, NW, E, false><<<grid, block, 0, st>>>(A, lda, Bs, NP, bias, mask, ldm, D1, D2,     \
-                                                                        ldd, dper, bits, C, ldc, M, N, K))
-  switch (epi) {
-    case kNone: M2F_X3NT(kNone); break;
-    case kBias: M2F_X3NT(kBias); break;
-    case kRelu: M2F_X3NT(kRelu); break;
-    case kBias | kRelu: M2F_X3NT(kBias | kRelu); break;
-    case kMask: M2F_X3NT(kMask); break;
-    case kBias | kMask: M2F_X3NT(kBias | kMask); break;
-    case kAdd: M2F_X3NT(kAdd); break;
-    case kBias | kAdd: M2F_X3NT(kBias | kAdd); break;
-    case kRelu | kBitsOut: M2F_X3NT(kRelu | kBitsOut); break;
-    case kBias | kRelu | kBitsOut: M2F_X3NT(kBias | kRelu | kBitsOut); break;
-    case kBitsIn: M2F_X3NT(kBitsIn); break;
-    case kBias | kBitsIn: M2F_X3NT(kBias | kBitsIn); break;
-    default: return m2f::fail(M2F_EINVAL, "m2f_gemm_f32x3_nt: epilogue %d", epi);
-  }
-#undef M2F_X3NT
+  if (!m2f::dispatch_one_of<kNone, kBias, kRelu, kBias | kRelu, kMask, kBias | kMask, kAdd, kBias | kAdd,
+                            kRelu | kBitsOut, kBias | kRelu | kBitsOut, kBitsIn, kBias | kBitsIn>(epi, [&](auto e) {
+        m2f::dispatch_bool(K % kBK == 0, [&](auto kfull) {
+          x3_nt_kernel<BN, NW, e.value, kfull.value><<<grid, block, 0, st>>>(A, lda, Bs, NP, bias, mask, ldm, D1, D2, ldd,
+                                                                            dper, bits, C, ldc, M, N, K);
+        });
+      }))
+    return m2f::fail(M2F_EINVAL, "m2f_gemm_f32x3_nt: epilogue %d", epi);
   return m2f::check_launch("m2f_gemm_f32x3_nt");
 }
 
@@ -756,20 +743,14 @@ extern "C" int m2f_gemm_f32x3_tn(const float* A, int64_t lda, const float* B, in
     float* cs = colsum ? cslab : nullptr;
     const int csum = colsum ? (p.swap ? 2 : 1) : 0;
     const bool mfull = M % kBK == 0;
-#define M2F_TN(NWV, MF, CS)                                                                                        \
-  x3_tn_kernel<NWV, MF, CS><<<grid, 64 * NWV, 0, st>>>(a, la, b, lb, M, p.n1, p.n2, p.rows, p.swap ? 1 : 0, slab, cs, \
-                                                       p.swap ? 1 : 0)
-#define M2F_TN_CS(NWV, MF) \
-  (csum == 0 ? M2F_TN(NWV, MF, 0) : csum == 1 ? M2F_TN(NWV, MF, 1) : M2F_TN(NWV, MF, 2))
-    if (p.nw == 3) {
-      if (mfull) M2F_TN_CS(3, true); else M2F_TN_CS(3, false);
-    } else if (p.nw == 8) {
-      if (mfull) M2F_TN_CS(8, true); else M2F_TN_CS(8, false);
-    } else {
-      if (mfull) M2F_TN_CS(4, true); else M2F_TN_CS(4, false);
-    }
-#undef M2F_TN_CS
-#undef M2F_TN
+    m2f::dispatch_one_of<3, 8, 4>(p.nw == 3 || p.nw == 8 ? p.nw : 4, [&](auto nw) {
+      m2f::dispatch_bool(mfull, [&](auto mf) {
+        m2f::dispatch_int<0, 2>(csum, [&](auto cs_mode) {
+          x3_tn_kernel<nw.value, mf.value, cs_mode.value><<<grid, 64 * nw.value, 0, st>>>(
+              a, la, b, lb, M, p.n1, p.n2, p.rows, p.swap ? 1 : 0, slab, cs, p.swap ? 1 : 0);
+        });
+      });
+    });
     if (int rc = m2f::check_launch(fn)) return rc;
   }
   const int64_t n = static_cast<int64_t>(N1) * N2;

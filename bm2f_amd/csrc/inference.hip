@@ -374,22 +374,13 @@ extern "C" int m2f_infer_semantic(const void* logits, int dtype, const float* pr
   if (num_classes <= 0) return m2f::fail(M2F_EINVAL, "%s: num_classes must be positive", fn);
   if (num_classes > kMaxK) return m2f::fail(M2F_EUNSUPPORTED, "%s: num_classes %d > %d", fn, num_classes, kMaxK);
   hipStream_t st = static_cast<hipStream_t>(stream);
-#define M2F_SEM(KT)                                                                                                  \
-  case KT:                                                                                                           \
-    return launch_semantic<KT>(logits, dtype, probs, sizes, batch, num_queries, num_classes, in_h, in_w, pad_h, pad_w, \
-                               out_h, out_w, semseg, labels, st)
-  switch ((num_classes + 31) / 32) {
-    M2F_SEM(1);
-    M2F_SEM(2);
-    M2F_SEM(3);
-    M2F_SEM(4);
-    M2F_SEM(5);
-    M2F_SEM(6);
-    M2F_SEM(7);
-    M2F_SEM(8);
-  }
-#undef M2F_SEM
-  return m2f::fail(M2F_EUNSUPPORTED, "%s: num_classes %d", fn, num_classes);
+  int rc = M2F_OK;
+  if (!m2f::dispatch_one_of<1, 2, 3, 4, 5, 6, 7, 8>((num_classes + 31) / 32, [&](auto kt) {
+        rc = launch_semantic<kt.value>(logits, dtype, probs, sizes, batch, num_queries, num_classes, in_h, in_w, pad_h,
+                                       pad_w, out_h, out_w, semseg, labels, st);
+      }))
+    return m2f::fail(M2F_EUNSUPPORTED, "%s: num_classes %d", fn, num_classes);
+  return rc;
 }
 
 extern "C" int m2f_infer_panoptic_pass(const void* logits, int dtype, const int32_t* keep_idx, const float* keep_score,

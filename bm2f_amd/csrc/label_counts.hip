@@ -236,15 +236,10 @@ int launch(const char* fn, bool lds, int lds_bins, unsigned grid, hipStream_t st
   return m2f::check_launch(fn);
 }
 
-template <class TA, class... Args>
-int launch_b(const char* fn, int b_bytes, Args... args) {
-  switch (b_bytes) {
-    case 1: return launch<TA, uint8_t>(fn, args...);
-    case 2: return launch<TA, int16_t>(fn, args...);
-    case 4: return launch<TA, int32_t>(fn, args...);
-    default: return launch<TA, int64_t>(fn, args...);
-  }
-}
+// the label type of BYTES bytes per element
+template <int BYTES>
+using Label = std::conditional_t<BYTES == 1, uint8_t,
+                                 std::conditional_t<BYTES == 2, int16_t, std::conditional_t<BYTES == 4, int32_t, int64_t>>>;
 
 }  // namespace
 
@@ -287,15 +282,12 @@ extern "C" int m2f_label_pair_counts_ragged(const void* a, int a_bytes, int64_t 
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned grid = static_cast<unsigned>(num_blocks);
   const int lds_bins = static_cast<int>(max_bins < kLdsBins ? max_bins : kLdsBins);
-  switch (a_bytes) {
-    case 1:
-      return launch_b<uint8_t>(fn, b_bytes, lds, lds_bins, grid, st, a, a_elems, b, b_elems, images, num_images, ids,
-                               total_ids, blocks, ign, out, out_len, bad);
-    case 2:
-      return launch_b<int16_t>(fn, b_bytes, lds, lds_bins, grid, st, a, a_elems, b, b_elems, images, num_images, ids,
-                               total_ids, blocks, ign, out, out_len, bad);
-    default:
-      return launch_b<int32_t>(fn, b_bytes, lds, lds_bins, grid, st, a, a_elems, b, b_elems, images, num_images, ids,
-                               total_ids, blocks, ign, out, out_len, bad);
-  }
+  int rc = M2F_OK;
+  m2f::dispatch_one_of<1, 2, 4>(a_bytes, [&](auto ab) {     // both widths were checked above
+    m2f::dispatch_one_of<1, 2, 4, 8>(b_bytes, [&](auto bb) {
+      rc = launch<Label<ab.value>, Label<bb.value>>(fn, lds, lds_bins, grid, st, a, a_elems, b, b_elems, images,
+                                                    num_images, ids, total_ids, blocks, ign, out, out_len, bad);
+    });
+  });
+  return rc;
 }

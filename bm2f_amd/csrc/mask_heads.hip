@@ -518,12 +518,9 @@ __global__ void __launch_bounds__(256, 2) mask_df_kernel(DfHeads heads, const T*
 
 template <typename T>
 int launch_mask_heads(const MhArgs& a, int QT, hipStream_t st, unsigned grid) {
-  switch (QT) {
-#define M2F_MH(N) case N: mask_heads_kernel<T, N><<<grid, kThreads, 0, st>>>(a); break;
-    M2F_MH(1) M2F_MH(2) M2F_MH(3) M2F_MH(4) M2F_MH(5) M2F_MH(6) M2F_MH(7) M2F_MH(8)
-#undef M2F_MH
-    default: return m2f::fail(M2F_EUNSUPPORTED, "m2f_mask_heads_fwd: %d queries (at most 256)", 32 * QT);
-  }
+  if (!m2f::dispatch_one_of<1, 2, 3, 4, 5, 6, 7, 8>(
+          QT, [&](auto qt) { mask_heads_kernel<T, qt.value><<<grid, kThreads, 0, st>>>(a); }))
+    return m2f::fail(M2F_EUNSUPPORTED, "m2f_mask_heads_fwd: %d queries (at most 256)", 32 * QT);
   return M2F_OK;
 }
 
@@ -562,11 +559,12 @@ extern "C" int m2f_mask_heads_fwd(int dtype, const void* embed, const void* feat
   a.ngroups = a.off + (height - a.off + 1) / 2;
   a.ncol = (width + kCols - 1) / kCols;
   const int64_t nblocks = static_cast<int64_t>(batch) * frames * a.ngroups * a.ncol;
-  if (nblocks > 0x7fffffff) return m2f::fail(M2F_EUNSUPPORTED, "%s: too many workgroups", fn);
+  unsigned grid;
+  int rc = m2f::grid_1d(nblocks, fn, &grid);
+  if (rc) return rc;
   const int QT = (num_queries + 31) / 32;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = dtype == M2F_BF16 ? launch_mask_heads<__bf16>(a, QT, st, static_cast<unsigned>(nblocks))
-                                   : launch_mask_heads<_Float16>(a, QT, st, static_cast<unsigned>(nblocks));
+  m2f::dispatch_half(dtype, [&](auto t) { rc = launch_mask_heads<typename decltype(t)::type>(a, QT, st, grid); });
   if (rc) return rc;
   return m2f::check_launch(fn);
 }
@@ -595,13 +593,9 @@ int launch_de(const void* G, const void* F, int B, int Q, int64_t N, float* part
   const T* g = static_cast<const T*>(G);
   const T* f = static_cast<const T*>(F);
   // two groups of 4 waves split the query tiles: QT = 1 (<= 64 queries), 2 (<= 128), 4 (<= 256)
-  if (Q <= 64)
-    mask_de_kernel<T, 1><<<grid, kDeThreads, 0, st>>>(g, f, Q, N, ks, splits, part);
-  else if (Q <= 128)
-    mask_de_kernel<T, 2><<<grid, kDeThreads, 0, st>>>(g, f, Q, N, ks, splits, part);
-  else if (Q <= 256)
-    mask_de_kernel<T, 4><<<grid, kDeThreads, 0, st>>>(g, f, Q, N, ks, splits, part);
-  else
+  if (!m2f::dispatch_one_of<1, 2, 4>(Q <= 64 ? 1 : Q <= 128 ? 2 : Q <= 256 ? 4 : 0, [&](auto qt) {
+        mask_de_kernel<T, qt.value><<<grid, kDeThreads, 0, st>>>(g, f, Q, N, ks, splits, part);
+      }))
     return m2f::fail(M2F_EUNSUPPORTED, "m2f_mask_heads_bwd_embed: %d queries (at most 256)", Q);
   const int64_t per_b = static_cast<int64_t>(Q) * 256, total = per_b * B;
   mask_de_reduce_kernel<T><<<m2f::ceil_div(total, 256), 256, 0, st>>>(part, splits, per_b, total, static_cast<T*>(de));
@@ -632,8 +626,10 @@ extern "C" int m2f_mask_heads_bwd_embed(int dtype, const void* grad_masks, const
                                                static_cast<long long>(workspace_bytes), static_cast<long long>(need));
   hipStream_t st = static_cast<hipStream_t>(stream);
   float* part = static_cast<float*>(workspace);
-  const int rc = dtype == M2F_BF16 ? launch_de<__bf16>(grad_masks, feats, batch, num_queries, n, part, grad_embed, st)
-                                   : launch_de<_Float16>(grad_masks, feats, batch, num_queries, n, part, grad_embed, st);
+  int rc = M2F_OK;
+  m2f::dispatch_half(dtype, [&](auto t) {
+    rc = launch_de<typename decltype(t)::type>(grad_masks, feats, batch, num_queries, n, part, grad_embed, st);
+  });
   if (rc) return rc;
   return m2f::check_launch(fn);
 }
@@ -656,21 +652,20 @@ extern "C" int m2f_mask_heads_bwd_feats(int dtype, const void* const* grad_masks
   if (!m2f::aligned(embed_t, 16) || !m2f::aligned(grad_feats, 16)) return m2f::fail(M2F_EINVAL, "%s: alignment", fn);
   const int ncol = static_cast<int>((n + kDfCols - 1) / kDfCols);
   const int64_t nblk = static_cast<int64_t>(ncol) * batch;
-  if (nblk > 0x7fffffff) return m2f::fail(M2F_EUNSUPPORTED, "%s: too many workgroups", fn);
+  unsigned g;
+  if (int rc = m2f::grid_1d(nblk, fn, &g)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (out_dtype != dtype && out_dtype != M2F_F32) return m2f::fail(M2F_EUNSUPPORTED, "%s: out dtype %d", fn, out_dtype);
-  const unsigned g = static_cast<unsigned>(nblk);
   const bool ks4 = m2f::option(m2f::kOptMaskDfStage, 4) >= 4;  // k-steps per LDS stage: 4 (default) or 1
-#define M2F_DF(T, O)                                                                                                    \
-  (ks4 ? mask_df_kernel<T, O, 4><<<g, 256, 0, st>>>(h, static_cast<const T*>(embed_t), heads, num_queries,             \
-                                                    padded_queries, n, ncol, static_cast<O*>(grad_feats))              \
-       : mask_df_kernel<T, O, 1><<<g, 256, 0, st>>>(h, static_cast<const T*>(embed_t), heads, num_queries,             \
-                                                    padded_queries, n, ncol, static_cast<O*>(grad_feats)))
-  if (dtype == M2F_BF16) {
-    if (out_dtype == M2F_F32) M2F_DF(__bf16, float); else M2F_DF(__bf16, __bf16);
-  } else {
-    if (out_dtype == M2F_F32) M2F_DF(_Float16, float); else M2F_DF(_Float16, _Float16);
-  }
-#undef M2F_DF
+  m2f::dispatch_half(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    m2f::dispatch_bool(out_dtype == M2F_F32, [&](auto f32) {
+      using O = std::conditional_t<f32.value, float, T>;
+      m2f::dispatch_bool(ks4, [&](auto k4) {
+        mask_df_kernel<T, O, k4.value ? 4 : 1><<<g, 256, 0, st>>>(h, static_cast<const T*>(embed_t), heads, num_queries,
+                                                                 padded_queries, n, ncol, static_cast<O*>(grad_feats));
+      });
+    });
+  });
   return m2f::check_launch(fn);
 }

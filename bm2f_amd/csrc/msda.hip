@@ -2493,12 +2493,11 @@ template <bool FUSED>
 int launch_tiled_levels(const float* value, const float* loc, const float* attn, const FrontEnd& fe, const float* gout,
                         const TileGeom& geo, size_t lds, int threads, const Dims& d, float* gv, float* gl, float* ga,
                         hipStream_t st, const DetBufs& det = DetBufs{}) {
-  switch (d.L) {
-    case 1: return launch_tiled<1, FUSED>(value, loc, attn, fe, gout, geo, lds, threads, d, gv, gl, ga, det, st);
-    case 2: return launch_tiled<2, FUSED>(value, loc, attn, fe, gout, geo, lds, threads, d, gv, gl, ga, det, st);
-    case 3: return launch_tiled<3, FUSED>(value, loc, attn, fe, gout, geo, lds, threads, d, gv, gl, ga, det, st);
-    default: return launch_tiled<4, FUSED>(value, loc, attn, fe, gout, geo, lds, threads, d, gv, gl, ga, det, st);
-  }
+  int rc = M2F_OK;
+  m2f::dispatch_int<1, 4>(d.L, [&](auto lt) {
+    rc = launch_tiled<lt.value, FUSED>(value, loc, attn, fe, gout, geo, lds, threads, d, gv, gl, ga, det, st);
+  });
+  return rc;
 }
 
 // -1: the tiled kernel does not apply (the caller takes another kernel); else the M2F status of its launch
@@ -2670,14 +2669,18 @@ bool make_fwd_lds_geom(const Dims& d, int proj_ld, const TileGeom& base, TileGeo
   return true;
 }
 
+// the three options that together select the LDS-window forward, fused or not
+bool fwd_windowed() {
+  return m2f::option(m2f::kOptMsdaFwdLds, 1) != 0 && m2f::option(m2f::kOptMsdaFwdQuad, 1) != 0 &&
+         m2f::option(m2f::kOptMsdaFwdTiled, 1) != 0;
+}
+
 // The reference op's forward (materialised loc / attn) on the LDS-window kernel: encoder layout with host shapes,
 // the options that select the windowed forward, and every byte offset under 2^31; false otherwise.
 bool launch_fwd_lds_unfused(const float* value, const float* loc, const float* attn, const Dims& d,
                             const int64_t* host_shapes, float* out, hipStream_t st) {
   if (!host_shapes || d.D != 32 || d.P != 4 || d.Lq != d.S || d.L < 1 || d.L > kTileMaxL) return false;
-  if (m2f::option(m2f::kOptMsdaFwdLds, 1) == 0 || m2f::option(m2f::kOptMsdaFwdQuad, 1) == 0 ||
-      m2f::option(m2f::kOptMsdaFwdTiled, 1) == 0)
-    return false;
+  if (!fwd_windowed()) return false;
   if (!m2f::aligned(loc, 8) || static_cast<int64_t>(d.N) * d.S * d.M * d.L * d.P * 8 >= (int64_t{1} << 31)) return false;
   TileGeom base{};
   base.L = d.L;
@@ -2699,12 +2702,9 @@ bool launch_fwd_lds_unfused(const float* value, const float* loc, const float* a
   if (nb > 0x7fffffff) return false;
   const unsigned tg = static_cast<unsigned>(nb);
   const FrontEnd fe{};
-  switch (d.L) {
-    case 1: msda_fused_fwd_lds<1, false><<<tg, kFwdLdsThreads, lds, st>>>(value, fe, geo, d.S, d.M, out, loc, attn); break;
-    case 2: msda_fused_fwd_lds<2, false><<<tg, kFwdLdsThreads, lds, st>>>(value, fe, geo, d.S, d.M, out, loc, attn); break;
-    case 3: msda_fused_fwd_lds<3, false><<<tg, kFwdLdsThreads, lds, st>>>(value, fe, geo, d.S, d.M, out, loc, attn); break;
-    default: msda_fused_fwd_lds<4, false><<<tg, kFwdLdsThreads, lds, st>>>(value, fe, geo, d.S, d.M, out, loc, attn); break;
-  }
+  m2f::dispatch_int<1, 4>(d.L, [&](auto lt) {
+    msda_fused_fwd_lds<lt.value, false><<<tg, kFwdLdsThreads, lds, st>>>(value, fe, geo, d.S, d.M, out, loc, attn);
+  });
   return true;
 }
 
@@ -2727,86 +2727,50 @@ static int fused_fwd(int hm, const char* fn, const float* value, const float* pr
   const bool boff31 = static_cast<int64_t>(d.N) * d.S * d.M * d.D * 4 < (int64_t{1} << 31);
   TileGeom lgeo;
   size_t llds = 0;
-  if (m2f::option(m2f::kOptMsdaFwdLds, 1) != 0 && m2f::option(m2f::kOptMsdaFwdQuad, 1) != 0 &&
-      m2f::option(m2f::kOptMsdaFwdTiled, 1) != 0 && m2f::option(m2f::kOptMsdaFwdPair, 0) != 0 &&
-      make_fwd_lds_geom(d, proj_ld, geo, lgeo, llds, true)) {
-    const int64_t nb = static_cast<int64_t>(lgeo.nty) * lgeo.ntx * d.M * d.N;
-    if (nb > 0x7fffffff) return m2f::fail(M2F_EUNSUPPORTED, "%s: too many workgroups", fn);
-    const unsigned tg = static_cast<unsigned>(nb);
-#define M2F_FP(LT) msda_fused_fwd_pair<LT><<<tg, kFwdPairThreads, 0, st>>>(value, fe, lgeo, d.S, d.M, output)
-    switch (d.L) {
-      case 1: M2F_FP(1); break;
-      case 2: M2F_FP(2); break;
-      case 3: M2F_FP(3); break;
-      default: M2F_FP(4); break;
-    }
-#undef M2F_FP
+  unsigned tg;
+  const bool windowed = fwd_windowed();
+  if (windowed && m2f::option(m2f::kOptMsdaFwdPair, 0) != 0 && make_fwd_lds_geom(d, proj_ld, geo, lgeo, llds, true)) {
+    if ((rc = m2f::grid_1d(static_cast<int64_t>(lgeo.nty) * lgeo.ntx * d.M * d.N, fn, &tg))) return rc;
+    m2f::dispatch_int<1, 4>(d.L, [&](auto lt) {
+      msda_fused_fwd_pair<lt.value><<<tg, kFwdPairThreads, 0, st>>>(value, fe, lgeo, d.S, d.M, output);
+    });
     return m2f::check_launch(fn);
   }
-  if (m2f::option(m2f::kOptMsdaFwdLds, 1) != 0 && m2f::option(m2f::kOptMsdaFwdQuad, 1) != 0 &&
-      m2f::option(m2f::kOptMsdaFwdTiled, 1) != 0 && make_fwd_lds_geom(d, proj_ld, geo, lgeo, llds)) {
-    const int64_t nb = static_cast<int64_t>(lgeo.nty) * lgeo.ntx * d.M * d.N;
-    if (nb > 0x7fffffff) return m2f::fail(M2F_EUNSUPPORTED, "%s: too many workgroups", fn);
-    const unsigned tg = static_cast<unsigned>(nb);
-#define M2F_FL(LT) msda_fused_fwd_lds<LT><<<tg, kFwdLdsThreads, llds, st>>>(value, fe, lgeo, d.S, d.M, output)
-    switch (d.L) {
-      case 1: M2F_FL(1); break;
-      case 2: M2F_FL(2); break;
-      case 3: M2F_FL(3); break;
-      default: M2F_FL(4); break;
-    }
-#undef M2F_FL
+  if (windowed && make_fwd_lds_geom(d, proj_ld, geo, lgeo, llds)) {
+    if ((rc = m2f::grid_1d(static_cast<int64_t>(lgeo.nty) * lgeo.ntx * d.M * d.N, fn, &tg))) return rc;
+    m2f::dispatch_int<1, 4>(d.L, [&](auto lt) {
+      msda_fused_fwd_lds<lt.value><<<tg, kFwdLdsThreads, llds, st>>>(value, fe, lgeo, d.S, d.M, output);
+    });
     return m2f::check_launch(fn);
   }
   if (boff31 && d.Lq == d.S && m2f::option(m2f::kOptMsdaFwdQuad, 1) != 0 && m2f::option(m2f::kOptMsdaFwdTiled, 1) != 0) {
     int64_t T = 0;
     for (int l = 0; l < d.L; ++l) T += static_cast<int64_t>((geo.H[l] + 7) / 8) * ((geo.W[l] + 7) / 8);
-    const int64_t nb = T * d.M * d.N;
-    if (nb > 0x7fffffff) return m2f::fail(M2F_EUNSUPPORTED, "%s: too many workgroups", fn);
-    const unsigned tg = static_cast<unsigned>(nb);
+    if ((rc = m2f::grid_1d(T * d.M * d.N, fn, &tg))) return rc;
     const int pb = m2f::option(m2f::kOptMsdaFwdPb, 2);  // points per load batch (1, 2 or 4)
-#define M2F_FQ(LT)                                                                                       \
-  (pb == 1   ? msda_fused_fwd_q4<LT, 1><<<tg, 256, 0, st>>>(value, fe, geo, d.S, d.M, output)            \
-   : pb >= 4 ? msda_fused_fwd_q4<LT, 4><<<tg, 256, 0, st>>>(value, fe, geo, d.S, d.M, output)            \
-             : msda_fused_fwd_q4<LT, 2><<<tg, 256, 0, st>>>(value, fe, geo, d.S, d.M, output))
-    switch (d.L) {
-      case 1: M2F_FQ(1); break;
-      case 2: M2F_FQ(2); break;
-      case 3: M2F_FQ(3); break;
-      default: M2F_FQ(4); break;
-    }
-#undef M2F_FQ
+    m2f::dispatch_int<1, 4>(d.L, [&](auto lt) {
+      m2f::dispatch_one_of<1, 2, 4>(pb == 1 ? 1 : pb >= 4 ? 4 : 2, [&](auto pbt) {
+        msda_fused_fwd_q4<lt.value, pbt.value><<<tg, 256, 0, st>>>(value, fe, geo, d.S, d.M, output);
+      });
+    });
     return m2f::check_launch(fn);
   }
-  if (m2f::option(m2f::kOptMsdaFwdTiled, 1) != 0 && d.Lq == d.S) {
+  const bool tiled = m2f::option(m2f::kOptMsdaFwdTiled, 1) != 0 && d.Lq == d.S;
+  if (tiled) {
     int64_t T = 0;
     for (int l = 0; l < d.L; ++l) T += static_cast<int64_t>((geo.H[l] + 3) / 4) * ((geo.W[l] + 7) / 8);
-    const int64_t nb = T * d.M * d.N;
-    if (nb > 0x7fffffff) return m2f::fail(M2F_EUNSUPPORTED, "%s: too many workgroups", fn);
-    const unsigned tg = static_cast<unsigned>(nb);
-#define M2F_FFT(LT)                                                                                           \
-  (off32 ? msda_fused_fwd<LT, true, true><<<tg, 256, 0, st>>>(value, fe, geo, d.npairs(), d.S, d.M, d.Lq, output)  \
-         : msda_fused_fwd<LT, true, false><<<tg, 256, 0, st>>>(value, fe, geo, d.npairs(), d.S, d.M, d.Lq, output))
-    switch (d.L) {
-      case 1: M2F_FFT(1); break;
-      case 2: M2F_FFT(2); break;
-      case 3: M2F_FFT(3); break;
-      default: M2F_FFT(4); break;
-    }
-#undef M2F_FFT
-    return m2f::check_launch(fn);
+    if ((rc = m2f::grid_1d(T * d.M * d.N, fn, &tg))) return rc;
+  } else {
+    tg = m2f::ceil_div(d.npairs(), 32);
   }
-  const unsigned grid = m2f::ceil_div(d.npairs(), 32);
-#define M2F_FF(LT)                                                                                            \
-  (off32 ? msda_fused_fwd<LT, false, true><<<grid, 256, 0, st>>>(value, fe, geo, d.npairs(), d.S, d.M, d.Lq, output) \
-         : msda_fused_fwd<LT, false, false><<<grid, 256, 0, st>>>(value, fe, geo, d.npairs(), d.S, d.M, d.Lq, output))
-  switch (d.L) {
-    case 1: M2F_FF(1); break;
-    case 2: M2F_FF(2); break;
-    case 3: M2F_FF(3); break;
-    default: M2F_FF(4); break;
-  }
-#undef M2F_FF
+  m2f::dispatch_int<1, 4>(d.L, [&](auto lt) {
+    m2f::dispatch_bool(tiled, [&](auto ti) {
+      m2f::dispatch_bool(off32, [&](auto o32) {
+        msda_fused_fwd<lt.value, ti.value, o32.value><<<tg, 256, 0, st>>>(value, fe, geo, d.npairs(), d.S, d.M, d.Lq,
+                                                                          output);
+      });
+    });
+  });
   return m2f::check_launch(fn);
 }
 
@@ -2927,20 +2891,15 @@ extern "C" int m2f_diag_msda_bwd_stamps_f32(const float* value, const float* loc
   hipStream_t st = static_cast<hipStream_t>(stream);
   (void)m2f::zero_async(grad_value, static_cast<size_t>(d.N) * d.S * d.M * 32 * 4, st);
   const dim3 grid(geo.nty * geo.ntx * d.M * d.N);
-#define M2F_DIAG_LAUNCH(TPB, NF)                                                                                  \
-  do {                                                                                                           \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&msda_bwd_f32_tiled<3, false, TPB, false, false, true, NF>),      \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);                   \
-    msda_bwd_f32_tiled<3, false, TPB, false, false, true, NF><<<grid, TPB, lds, st>>>(value, loc, attn, FrontEnd{}, grad_output, \
-                                                                       geo, d.S, d.M, grad_value, grad_loc,     \
-                                                                       grad_attn, nullptr, nullptr, stamps);    \
-  } while (0)
-  if (threads == 1024) {
-    if (noflush) M2F_DIAG_LAUNCH(1024, true); else M2F_DIAG_LAUNCH(1024, false);
-  } else {
-    if (noflush) M2F_DIAG_LAUNCH(512, true); else M2F_DIAG_LAUNCH(512, false);
-  }
-#undef M2F_DIAG_LAUNCH
+  m2f::dispatch_one_of<1024, 512>(threads == 1024 ? 1024 : 512, [&](auto tpb) {
+    m2f::dispatch_bool(noflush != 0, [&](auto nf) {
+      auto* k = &msda_bwd_f32_tiled<3, false, tpb.value, false, false, true, nf.value>;
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                160 * 1024 - 1024);
+      k<<<grid, tpb.value, lds, st>>>(value, loc, attn, FrontEnd{}, grad_output, geo, d.S, d.M, grad_value, grad_loc,
+                                      grad_attn, nullptr, nullptr, stamps);
+    });
+  });
   return m2f::check_launch("m2f_diag_msda_bwd_stamps_f32");
 }
 #endif

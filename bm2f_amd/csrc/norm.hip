@@ -213,13 +213,9 @@ extern "C" int m2f_add_layernorm_fwd_f32(const float* a, const float* b, const f
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t want = (rows + kWaves - 1) / kWaves;
   const int grid = static_cast<int>(want < 256 * 64 ? want : 256 * 64);
-  const int nv = (C / 4 + 63) / 64;
-  switch (nv) {
-    case 1: add_ln_fwd_kernel<1><<<grid, kThreads, 0, st>>>(a, b, gamma, beta, rows, C, eps, y, mean, rstd); break;
-    case 2: add_ln_fwd_kernel<2><<<grid, kThreads, 0, st>>>(a, b, gamma, beta, rows, C, eps, y, mean, rstd); break;
-    case 3: add_ln_fwd_kernel<3><<<grid, kThreads, 0, st>>>(a, b, gamma, beta, rows, C, eps, y, mean, rstd); break;
-    default: add_ln_fwd_kernel<4><<<grid, kThreads, 0, st>>>(a, b, gamma, beta, rows, C, eps, y, mean, rstd); break;
-  }
+  m2f::dispatch_int<1, 4>((C / 4 + 63) / 64, [&](auto nv) {
+    add_ln_fwd_kernel<nv.value><<<grid, kThreads, 0, st>>>(a, b, gamma, beta, rows, C, eps, y, mean, rstd);
+  });
   return m2f::check_launch(fn);
 }
 
@@ -245,13 +241,9 @@ extern "C" int m2f_add_layernorm_bwd_f32(const float* grad_y, const float* a, co
     if (grad_beta) (void)m2f::zero_async(grad_beta, C * sizeof(float), st);
     return m2f::check_launch(fn);
   }
-  const int nv = (C / 4 + 63) / 64;
-  switch (nv) {
-    case 1: add_ln_bwd_kernel<1><<<nblocks, kThreads, 0, st>>>(grad_y, a, b, gamma, mean, rstd, rows, C, grad_x, part); break;
-    case 2: add_ln_bwd_kernel<2><<<nblocks, kThreads, 0, st>>>(grad_y, a, b, gamma, mean, rstd, rows, C, grad_x, part); break;
-    case 3: add_ln_bwd_kernel<3><<<nblocks, kThreads, 0, st>>>(grad_y, a, b, gamma, mean, rstd, rows, C, grad_x, part); break;
-    default: add_ln_bwd_kernel<4><<<nblocks, kThreads, 0, st>>>(grad_y, a, b, gamma, mean, rstd, rows, C, grad_x, part); break;
-  }
+  m2f::dispatch_int<1, 4>((C / 4 + 63) / 64, [&](auto nv) {
+    add_ln_bwd_kernel<nv.value><<<nblocks, kThreads, 0, st>>>(grad_y, a, b, gamma, mean, rstd, rows, C, grad_x, part);
+  });
   if (int rc = m2f::check_launch(fn)) return rc;
   if (grad_gamma || grad_beta) {
     ln_param_reduce_kernel<<<m2f::ceil_div(2 * C, 64), 256, 0, st>>>(part, nblocks, C, grad_gamma, grad_beta);

@@ -554,25 +554,16 @@ int launch_bwd(const void* qkv, const float* table, const void* dout, const floa
   return m2f::check_launch("m2f_window_attn_bwd");
 }
 
-// NT = ceil(ws^2 / 16) for ws = 2 .. 12 is one of 1, 2, 3, 4, 6, 7, 8, 9
-#define WATTN_BY_TILES(T, CALL)                                \
-  switch (tiles_of(G.ws)) {                                    \
-    case 1: return CALL<T, 1>;                                 \
-    case 2: return CALL<T, 2>;                                 \
-    case 3: return CALL<T, 3>;                                 \
-    case 4: return CALL<T, 4>;                                 \
-    case 6: return CALL<T, 6>;                                 \
-    case 7: return CALL<T, 7>;                                 \
-    case 8: return CALL<T, 8>;                                 \
-    case 9: return CALL<T, 9>;                                 \
-    default: return nullptr;                                   \
-  }
-
-using FwdFn = int (*)(const void*, const float*, void*, float*, const Geo&, float, hipStream_t);
-using BwdFn = int (*)(const void*, const float*, const void*, const float*, void*, float*, const Geo&, float,
-                      hipStream_t);
-template <typename T> FwdFn pick_fwd(const Geo& G) { WATTN_BY_TILES(T, &launch_fwd) }
-template <typename T> BwdFn pick_bwd(const Geo& G) { WATTN_BY_TILES(T, &launch_bwd) }
+// f(Tag<T>, NT) for the element type and NT = ceil(ws^2 / 16), which for ws = 2 .. 12 is one of 1, 2, 3, 4, 6, 7, 8, 9;
+// false, without a call, for any other dtype code or tile count
+template <typename F>
+bool by_type_and_tiles(int dtype, int ws, F&& f) {
+  bool built = false;
+  m2f::dispatch_float(dtype, [&](auto t) {
+    built = m2f::dispatch_one_of<1, 2, 3, 4, 6, 7, 8, 9>(tiles_of(ws), [&](auto nt) { f(t, nt); });
+  });
+  return built;
+}
 
 int64_t part_floats(const Geo& G) {
   const int TW = 2 * G.ws - 1;
@@ -598,10 +589,13 @@ extern "C" int m2f_window_attn_fwd(int dtype, const void* qkv, const float* tabl
     return m2f::fail(M2F_EINVAL, "%s: qkv and out must be 16-byte aligned", fn);
   if (batch == 0) return m2f::ok();
   const Geo G = make_geo(batch, heads, hp, wp, ws, shift);
-  FwdFn f = dtype == M2F_F32 ? pick_fwd<float>(G) : dtype == M2F_F16 ? pick_fwd<_Float16>(G)
-            : dtype == M2F_BF16 ? pick_fwd<__bf16>(G) : nullptr;
-  if (!f) return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype code %d", fn, dtype);
-  return f(qkv, table, out, lse, G, scale, static_cast<hipStream_t>(stream));
+  int rc = M2F_OK;
+  if (!by_type_and_tiles(dtype, ws, [&](auto t, auto nt) {
+        rc = launch_fwd<typename decltype(t)::type, nt.value>(qkv, table, out, lse, G, scale,
+                                                              static_cast<hipStream_t>(stream));
+      }))
+    return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype code %d", fn, dtype);
+  return rc;
 }
 
 extern "C" int m2f_window_attn_bwd(int dtype, const void* qkv, const float* table, const void* dout, const float* lse,
@@ -618,13 +612,15 @@ extern "C" int m2f_window_attn_bwd(int dtype, const void* qkv, const float* tabl
     return m2f::fail(M2F_EINVAL, "%s: workspace of %lld bytes, %lld needed", fn, static_cast<long long>(workspace_bytes),
                      static_cast<long long>(part_floats(G) * sizeof(float)));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  BwdFn f = dtype == M2F_F32 ? pick_bwd<float>(G) : dtype == M2F_F16 ? pick_bwd<_Float16>(G)
-            : dtype == M2F_BF16 ? pick_bwd<__bf16>(G) : nullptr;
-  if (!f) return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype code %d", fn, dtype);
   float* part = static_cast<float*>(workspace);
+  int rc = M2F_OK;
+  if (!by_type_and_tiles(dtype, ws, [&](auto t, auto nt) {
+        if (batch > 0)
+          rc = launch_bwd<typename decltype(t)::type, nt.value>(qkv, table, dout, lse, dqkv, part, G, scale, st);
+      }))
+    return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype code %d", fn, dtype);
+  if (rc) return rc;
   const int TW = 2 * ws - 1, TB = TW * TW;
-  if (batch > 0)
-    if (int rc = f(qkv, table, dout, lse, dqkv, part, G, scale, st)) return rc;
   // with no window the sums are empty: the kernel writes zeros
   wattn_dtable_kernel<<<dim3(m2f::ceil_div(TB, 64), heads), 64 * kSeg, 0, st>>>(part, dtable, batch * G.nWy * G.nWx,
                                                                                 heads, TB);

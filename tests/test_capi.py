@@ -3,6 +3,8 @@ import ctypes
 import os
 import re
 
+import pytest
+
 from conftest import ROOT
 
 
@@ -97,6 +99,38 @@ def test_shape_preconditions_rejected_without_gpu():
     # the 16-bit NHWC input-gradient epilogue writes 8 channels per store: output channels % 16 != 0 is refused
     rc = lib.m2f_conv_x3_io(p, 0, 0, p, None, p, 1, 1, 1, 24, 32, 16, 16, 1, 1, p, ctypes.c_int64(1 << 30), None)
     assert rc == 3 and b"output channels" in lib.m2f_last_error()
+
+
+_P = ctypes.c_void_p(1 << 20)    # aligned, non-null, never dereferenced: every call below returns before the device
+_WS = ctypes.c_int64(1 << 20)
+# entry point -> arguments with dtype code 99, sized so that no zero-size shortcut returns before the dtype test
+_BAD_DTYPE_CALLS = {
+    "m2f_bias_act_nchw": (_P, None, _P, 1, 8, 64, 99, 0, None),
+    "m2f_relu_bwd_sum": (_P, 1, _P, _P, 64, 99, None),
+    "m2f_sum_to_f32": (_P, 1, 64, 99, _P, None),
+    "m2f_maxpool3s2_nhwc": (0, _P, _P, _P, 1, 8, 8, 8, 99, None),
+    "m2f_maxpool3s2_fwd": (_P, _P, _P, 4, 8, 8, 99, None),
+    "m2f_maxpool3s2_bwd": (_P, _P, _P, 4, 8, 8, 99, None),
+    "m2f_colsum": (99, _P, 8, 8, _P, _WS, _P, None),
+    "m2f_attn_mask_bits": (_P, 99, 1, 4, 1, 8, 8, 8, 8, 0, _P, 2, None),
+    "m2f_masked_attn_fwd": (99, _P, _P, _P, _P, 1, 4, 64, 1, 32, 32, 64, 2, 0.25, _P, _P, _P, _WS, None),
+    "m2f_masked_attn_bwd": (99, _P, _P, _P, _P, _P, _P, _P, 1, 4, 64, 1, 32, 32, 64, 2, 0.25, _P, _P, _P, _P, _WS, None),
+    "m2f_mask_heads_fwd": (99, _P, _P, 1, 4, 32, 1, 8, 8, 0, 0, _P, None, 0, None),
+    "m2f_mask_heads_bwd_embed": (99, _P, _P, 1, 4, 256, 16, _P, _P, _WS, None),
+    "m2f_mask_heads_bwd_feats": (99, _P, 1, _P, 1, 4, 16, 256, 8, 0, _P, None),
+}
+
+
+@pytest.mark.parametrize("name", sorted(_BAD_DTYPE_CALLS))
+def test_unknown_dtype_rejected_without_gpu(name):
+    """An element-type code outside M2F_F32 / M2F_F16 / M2F_BF16 is refused as unsupported, with the code in the
+    message, by every entry point that tests its dtype before it touches the device."""
+    from bm2f_amd import _native
+    lib = _native.load()
+    rc = getattr(lib, name)(*_BAD_DTYPE_CALLS[name])
+    assert rc == 3, lib.m2f_last_error()                     # M2F_EUNSUPPORTED
+    assert b"dtype 99" in lib.m2f_last_error()
+    assert name.encode() in lib.m2f_last_error()
 
 
 def test_head_major_wb_rows():
