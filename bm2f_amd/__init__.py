@@ -13,6 +13,7 @@ from .coco_eval import (COCOEvalResult, COCOEvaluator, COCOGroundTruth, COCOPara
                         evaluate_coco)
 from .mask_iou import (mask_iou, mask_pair_counts, mask_pair_counts_ragged, rle_to_bits,  # noqa: F401
                        rle_to_bits_ragged)
+from .mask_boundary import boundary_bits_ragged, boundary_dilation, mask_to_boundary_bits  # noqa: F401
 from .label_counts import label_pair_counts, label_pair_counts_ragged  # noqa: F401
 from .panoptic_eval import (COCOPanopticEvaluator, PanopticGroundTruth, PQStat, evaluate_panoptic,  # noqa: F401
                             id2rgb, pq_from_counts, rgb2id)

@@ -126,6 +126,8 @@ _SIGNATURES = {
     "m2f_label_pair_counts_ragged": [_p, _i, _l, _p, _i, _l, _p, _i, _p, _l, _p, _l, _i, _i, _l, _i, _p, _l, _p, _p],
     "m2f_poly_crossings": [_p, _p, _p, _l, _l, _p, _p],
     "m2f_poly_decode_bits_ragged": [_p, _l, _p, _l, _p, _i, _p, _p, _p, _l, _p, _l, _p],
+    "m2f_bits_boundary_tiles": [_p, _p, _p],
+    "m2f_bits_boundary_ragged": [_p, _l, _i, _p, _p, _p, _p, _l, _i, _p, _p],
 }
 
 

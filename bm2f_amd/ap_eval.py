@@ -191,12 +191,16 @@ def _summarize(p, precision, recall):
     return stats
 
 
-def evaluate_units(p, unit, anns_of, results, counts_of, gt_area, dt_area, crowd_iou, result_cls=EvalResult):
+def evaluate_units(p, unit, anns_of, results, counts_of, gt_area, dt_area, crowd_iou, result_cls=EvalResult,
+                   second_counts_of=None):
     """The evaluation proper with normalised params ``p``.  ``anns_of`` maps a unit id to its annotations;
     ``counts_of(unit id, annotations, results of the unit)`` gives ``(inter, area_d, area_g)`` over all categories, rows in
     the order of those two lists, and is asked only for units that hold anything; ``gt_area(annotation)`` and
     ``dt_area(result, its row of area_d)`` fill ``avg_area``.  With ``crowd_iou`` the IoU with a crowd ground truth is
-    ``i / area(detection)`` (``maskUtils.iou(d, g, iscrowd)``).  -> ``result_cls`` (an :class:`EvalResult`)."""
+    ``i / area(detection)`` (``maskUtils.iou(d, g, iscrowd)``).  ``second_counts_of``, where given, is asked like
+    ``counts_of`` for a second triple (Boundary AP: the counts of the boundaries) and the IoU of a pair is the smaller
+    of the two triples' IoUs, each with the crowd rule on its own areas; the areas handed to ``dt_area`` stay those
+    of ``counts_of``.  -> ``result_cls`` (an :class:`EvalResult`)."""
     unit_ids, cats, maxDet = getattr(p, unit.ids_attr), set(p.catIds), p.maxDets[-1]
     dets_of = {}
     for index, r in enumerate(results):
@@ -206,6 +210,8 @@ def evaluate_units(p, unit, anns_of, results, counts_of, gt_area, dt_area, crowd
         anns, dets = anns_of.get(unitId, []), dets_of.get(unitId, [])
         if anns or dets:
             inter, area_d, area_g = counts_of(unitId, anns, [r for _, r in dets])
+            if second_counts_of is not None:
+                inter2, area_d2, area_g2 = second_counts_of(unitId, anns, [r for _, r in dets])
         for j, ann in enumerate(anns):
             if ann["category_id"] in cats:
                 gts_by.setdefault((unitId, ann["category_id"]), []).append(
@@ -225,8 +231,11 @@ def evaluate_units(p, unit, anns_of, results, counts_of, gt_area, dt_area, crowd
             if not rows_d or not rows_g:
                 ious[unitId, catId] = np.zeros([len(d), len(g)])
                 continue
-            ious[unitId, catId] = mask_iou(inter[np.ix_(rows_d, rows_g)], area_d[rows_d], area_g[rows_g],
-                                           iscrowd=[x["iscrowd"] for x in g] if crowd_iou else None)
+            crowd = [x["iscrowd"] for x in g] if crowd_iou else None
+            ious[unitId, catId] = mask_iou(inter[np.ix_(rows_d, rows_g)], area_d[rows_d], area_g[rows_g], iscrowd=crowd)
+            if second_counts_of is not None:
+                ious[unitId, catId] = np.minimum(ious[unitId, catId], mask_iou(
+                    inter2[np.ix_(rows_d, rows_g)], area_d2[rows_d], area_g2[rows_g], iscrowd=crowd))
 
     evalImgs = [_evaluate_unit(p, unit, gts_by.get((unitId, catId), []), dts_by.get((unitId, catId), []),
                                ious[unitId, catId], unitId, catId, aRng, maxDet)

@@ -23,6 +23,10 @@ pass ``polygons="rasterize"``.  Then a batch's RLE masks and polygon annotations
 (``polygon.pair_counts_ragged``): still one upload, one copy and a number of launches that does not depend on the
 batch.  The rasteriser is ``bm2f_amd.polygon``'s restatement of ``rleFrPoly``; it has not been run against
 pycocotools itself.  A batch without polygons takes the RLE path unchanged.
+
+``iou_type="boundary"`` is Boundary AP: the IoU of a pair is the smaller of its mask IoU and the IoU of the two
+masks' boundaries (``bm2f_amd.mask_boundary`` restates the definition and holds the batch step, which adds one launch
+of the boundary kernel and a second pair count to the launches above).
 """
 from __future__ import annotations
 
@@ -33,6 +37,7 @@ import numpy as np
 
 from .ap_eval import IMAGE, APEvaluator, EvalResult, evaluate_units, normalize_params
 from .evaluation import instances_to_coco_json
+from .mask_boundary import boundary_dilation, boundary_pair_counts_ragged, boundary_tiles
 from .mask_iou import MAX_RAGGED_WORDS, rle_pair_counts_ragged
 from .polygon import check_annotation, is_polygon, pair_counts_ragged
 
@@ -141,12 +146,22 @@ def image_batches(gt, img_ids, dets_of, batch_bytes):
     return batches
 
 
-def _segm_counts(gt, img_ids, dets_of, device, batch_bytes):
+def _segm_counts(gt, img_ids, dets_of, device, batch_bytes, dilation_ratio=None):
     """-> {image id: (inter (D, G), area_d (D,), area_g (G,))} over all categories, G in the order of
-    ``gt.img_to_anns``."""
-    counts = {}
+    ``gt.img_to_anns``.  With a ``dilation_ratio`` (Boundary AP) -> that dict and the same of the masks' boundaries;
+    a batch then holds a second buffer of boundary planes, so it takes half of ``batch_bytes`` of mask planes."""
+    counts, edge_counts = {}, {}
     for img_id in img_ids:                                            # every check before the first launch
         _check_segm(gt, img_id, dets_of.get(img_id, []), gt.img_to_anns.get(img_id, []))
+    if dilation_ratio is not None:
+        d_max = boundary_tiles()[2]
+        for img_id in img_ids:
+            img = gt.imgs[img_id]
+            if dets_of.get(img_id) or gt.img_to_anns.get(img_id):
+                d = boundary_dilation(img["height"], img["width"], dilation_ratio)
+                if d > d_max:
+                    raise ValueError(f"image {img_id}: a dilation of {d} pixels is more than the {d_max} supported")
+        batch_bytes = max(int(batch_bytes) // 2, 1)
     for batch in image_batches(gt, img_ids, dets_of, batch_bytes):
         rles, groups, sizes, names = [], [], [], []
         for img_id in batch:
@@ -159,13 +174,17 @@ def _segm_counts(gt, img_ids, dets_of, device, batch_bytes):
             names += [None] * len(dets) + [f"annotation {a.get('id')}" for a in anns]
             groups.append((size[0], size[1], np.arange(n0, n0 + len(dets)),
                            np.arange(n0 + len(dets), n0 + len(dets) + len(anns))))
-        if any(s is not None for s in sizes):                         # polygon ground truth in this batch
+        if dilation_ratio is not None:
+            batch_counts, batch_edges = boundary_pair_counts_ragged(rles, groups, device=device, sizes=sizes,
+                                                                    names=names, dilation_ratio=dilation_ratio)
+            edge_counts.update(zip(batch, batch_edges))
+        elif any(s is not None for s in sizes):                       # polygon ground truth in this batch
             batch_counts = pair_counts_ragged(rles, groups, device=device, sizes=sizes, names=names)
         else:
             batch_counts = rle_pair_counts_ragged(rles, groups, device=device)
         for img_id, c in zip(batch, batch_counts):
             counts[img_id] = c
-    return counts
+    return counts if dilation_ratio is None else (counts, edge_counts)
 
 
 def _xywh(items, what, img_id):
@@ -195,10 +214,17 @@ def _bbox_counts(gt, img_ids, dets_of):
 # evaluate
 # -------------------------------------------------------------------------------------------------------------------
 def evaluate_coco(gt, results, iou_type="segm", device=None, params=None,
-                  batch_bytes=DEFAULT_BATCH_BYTES) -> COCOEvalResult:
+                  batch_bytes=DEFAULT_BATCH_BYTES, dilation_ratio=0.02) -> COCOEvalResult:
     """gt: a :class:`COCOGroundTruth`; results: the list ``instances_to_coco_json`` writes (``image_id``,
     ``category_id``, ``score``, ``segmentation`` as RLE, ``bbox`` as xywh).  ``iou_type`` is ``"segm"`` (masks, built
-    and counted on ``device`` in batches of ``batch_bytes`` of planes) or ``"bbox"`` (numpy).  Only ``useCats=1``.
+    and counted on ``device`` in batches of ``batch_bytes`` of planes), ``"boundary"`` or ``"bbox"`` (numpy).  Only
+    ``useCats=1``.
+
+    ``"boundary"`` is Boundary AP (``COCOeval`` of the boundary-iou-api with ``iouType="boundary"``, restated in
+    ``bm2f_amd.mask_boundary``; that package has not been run against this code): the IoU of a pair is
+    ``min(mask IoU, IoU of the two masks' boundaries)`` with ``d`` from ``dilation_ratio`` and each image's size, both
+    with the crowd rule; everything else is as for ``"segm"`` (areas are mask areas, ``bbox`` fields are ignored).
+    The boundary planes are a second buffer in every batch, counted in ``batch_bytes``.
 
     The rules (ordering, the ``maxDets[-1]`` cut per (image, category), matching thresholds and ties, the crowd
     re-match, the break on ignore, float32 accumulation, the -1 conventions, the 12 statistics) are listed in
@@ -206,20 +232,25 @@ def evaluate_coco(gt, results, iou_type="segm", device=None, params=None,
 
     Raises ValueError, before any launch, when a result names an unknown image, its mask size is not the image's, or
     (``bbox``) it has no ``bbox``."""
-    if iou_type not in ("segm", "bbox"):
-        raise NotImplementedError("iou_type must be 'segm' or 'bbox'")
+    if iou_type not in ("segm", "bbox", "boundary"):
+        raise NotImplementedError("iou_type must be 'segm', 'boundary' or 'bbox'")
     p = normalize_params(IMAGE, params if params is not None else COCOParams(iou_type), gt.image_ids(),
                          gt.category_ids(), results, "results name images the ground truth does not hold")
     p.iouType = iou_type
     dets_of = {}
     for r in results:
         dets_of.setdefault(r["image_id"], []).append(r)
+    second = None
     if iou_type == "segm":
         counts = _segm_counts(gt, p.imgIds, dets_of, device, batch_bytes)
+    elif iou_type == "boundary":
+        counts, edges = _segm_counts(gt, p.imgIds, dets_of, device, batch_bytes, dilation_ratio=float(dilation_ratio))
+        second = lambda imgId, anns, dets: edges[imgId]               # noqa: E731
     else:
         counts = _bbox_counts(gt, p.imgIds, dets_of)
     return evaluate_units(p, IMAGE, gt.img_to_anns, results, lambda imgId, anns, dets: counts[imgId],
-                          lambda ann: ann["area"], lambda r, area: area, crowd_iou=True, result_cls=COCOEvalResult)
+                          lambda ann: ann["area"], lambda r, area: area, crowd_iou=True, result_cls=COCOEvalResult,
+                          second_counts_of=second)
 
 
 # -------------------------------------------------------------------------------------------------------------------
@@ -233,12 +264,16 @@ class COCOEvaluator(APEvaluator):
     :class:`MaskFormerInference` (``instance_rle=True`` or plain masks), written with ``instances_to_coco_json``.
     ``results`` is the accumulated ``coco_instances_results.json`` list with the head's contiguous category ids;
     ``evaluate`` maps them back through ``thing_dataset_id_to_contiguous_id`` (instance_evaluation.py:52-70).
-    ``polygons`` is passed to :class:`COCOGroundTruth` when ``ground_truth`` is not one already."""
+    ``polygons`` is passed to :class:`COCOGroundTruth` when ``ground_truth`` is not one already.  ``tasks`` may hold
+    ``"boundary"`` (Boundary AP with ``dilation_ratio``, see :func:`evaluate_coco`), reported under the same metric
+    names."""
 
     def __init__(self, ground_truth, thing_dataset_id_to_contiguous_id=None, class_names=None, device=None,
-                 params=None, tasks=("segm",), batch_bytes=DEFAULT_BATCH_BYTES, polygons="refuse"):
+                 params=None, tasks=("segm",), batch_bytes=DEFAULT_BATCH_BYTES, polygons="refuse",
+                 dilation_ratio=0.02):
         self.tasks = tuple(tasks)
         self.batch_bytes = batch_bytes
+        self.dilation_ratio = dilation_ratio
         gt = (ground_truth if isinstance(ground_truth, COCOGroundTruth)
               else COCOGroundTruth(ground_truth, polygons=polygons))
         super().__init__(gt, thing_dataset_id_to_contiguous_id, class_names, device, params)
@@ -272,12 +307,13 @@ class COCOEvaluator(APEvaluator):
         predictions = self._mapped()
         out = {}
         for task in sorted(self.tasks):
-            assert task in {"bbox", "segm"}, f"Got unknown task: {task}!"
+            assert task in {"bbox", "segm", "boundary"}, f"Got unknown task: {task}!"
             if len(predictions) == 0:
                 self.last[task] = None
             else:
                 params = copy.deepcopy(self.params) if self.params is not None else None
                 self.last[task] = evaluate_coco(self.gt, predictions, iou_type=task, device=self.device,
-                                                params=params, batch_bytes=self.batch_bytes)
+                                                params=params, batch_bytes=self.batch_bytes,
+                                                dilation_ratio=self.dilation_ratio)
             out[task] = self._derive(self.last[task])
         return out
