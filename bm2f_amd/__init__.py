@@ -17,6 +17,7 @@ from .mask_boundary import boundary_bits_ragged, boundary_dilation, mask_to_boun
 from .label_counts import label_pair_counts, label_pair_counts_ragged  # noqa: F401
 from .panoptic_eval import (COCOPanopticEvaluator, PanopticGroundTruth, PQStat, evaluate_panoptic,  # noqa: F401
                             id2rgb, pq_from_counts, rgb2id)
+from .tta import SemanticSegmentorWithTTA, semantic_inference_tta, tta_view_sizes  # noqa: F401
 from .sem_seg_eval import SemSegEvaluator, evaluate_sem_seg, sem_seg_metrics  # noqa: F401
 from .polygon import (ann_to_rle, convert_polygons_to_rle, polygon_crossings, polygons_to_bits,  # noqa: F401
                       polygons_to_bits_ragged, polygons_to_rle)

@@ -104,6 +104,7 @@ _SIGNATURES = {
     "m2f_point_loss_fwd": [_p, _i, _l, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p],
     "m2f_point_loss_bwd": [_p, _i, _l, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p],
     "m2f_infer_semantic": [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p],
+    "m2f_infer_semantic_tta": [_p, _i, _l, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p],
     "m2f_infer_panoptic_pass": [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p],
     "m2f_infer_instance": [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p],
     "m2f_infer_video": [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],

@@ -590,6 +590,31 @@ int m2f_point_loss_bwd(const void* masks, int dtype, int64_t n_planes, int H, in
 int m2f_infer_semantic(const void* logits, int dtype, const float* probs, const int32_t* sizes, int batch,
                        int num_queries, int num_classes, int in_h, int in_w, int pad_h, int pad_w, int out_h,
                        int out_w, float* semseg, int16_t* labels, void* stream);
+/* Semantic test-time augmentation (SemanticSegmentorWithTTA._inference_one_image,
+ * test_time_augmentation.py:71-98): the mean over the num_views augmented views of ONE image of each
+ * view's semantic scores, mirrored back where the view was flipped, in one launch:
+ *   semseg (K, out_h, out_w) fp32 = (sum_v sum_q probs[v, k, q] * s_vq(y, flip_v ? out_w - 1 - x : x)) / V.
+ * logits  logits_numel elements of `dtype`: one flat buffer, or the address range that spans the
+ *         views' separate allocations, holding every view's (Q, h_v, w_v) low-resolution mask
+ *         logits; only the views' own elements are read;
+ * probs   (V, K, Q) fp32, softmax(pred_logits_v)[..., :-1] transposed, as m2f_infer_semantic takes it;
+ * views   (V, M2F_TTA_VIEW_FIELDS) int64 device table, one row per view:
+ *         [element offset of the view's logits in `logits`, h, w, pad_h, pad_w, Hc, Wc, flip];
+ *         Hc, Wc are clamped to [1, pad_*]; a row with a non-positive size, or whose Q * h * w
+ *         elements do not lie inside the buffer, contributes nothing (the divisor stays V);
+ * before  nonzero: s = sigmoid of the chained logit (resize to the pad, crop, resize to the output;
+ *         sem_seg_postprocess_before_inference).  Zero: the reference's default order, the view's
+ *         scores are computed on the crop and resized after, s = the stage-2 bilinear blend of the
+ *         sigmoids of the four stage-1 logits.  Both orders skip stage 2 when (Hc, Wc) equals
+ *         (out_h, out_w).
+ * With labels != NULL it writes labels (out_h, out_w) int16 = argmax_k (first maximum; a pixel whose
+ * scores are all NaN gets -1) and no (K, out_h, out_w) buffer exists anywhere; semseg may be NULL.
+ * The sum runs in a fixed order without atomics: bitwise repeatable.  1 <= V <= 32, K <= 256,
+ * Q <= 256, else M2F_EUNSUPPORTED; null pointers M2F_EINVAL. */
+enum { M2F_TTA_VIEW_FIELDS = 8 };
+int m2f_infer_semantic_tta(const void* logits, int dtype, int64_t logits_numel, const float* probs,
+                           const int64_t* views, int num_views, int num_queries, int num_classes, int out_h,
+                           int out_w, int before, float* semseg, int16_t* labels, void* stream);
 /* The pixel pass of panoptic_inference (:515-571).  keep_idx / keep_score (B, Q): the kept queries
  * of each image in ascending order and their scores, num_keep (B,) int32 how many.  Outputs:
  * winner (B, out_h, out_w) int16 = index into the kept list of argmax_k score_k * sigmoid(logit_k)
