@@ -14,7 +14,8 @@ from .coco_eval import (COCOEvalResult, COCOEvaluator, COCOGroundTruth, COCOPara
 from .mask_iou import (mask_iou, mask_pair_counts, mask_pair_counts_ragged, rle_to_bits,  # noqa: F401
                        rle_to_bits_ragged)
 from .mask_boundary import boundary_bits_ragged, boundary_dilation, mask_to_boundary_bits  # noqa: F401
-from .label_counts import label_pair_counts, label_pair_counts_ragged  # noqa: F401
+from .label_counts import label_histogram_ragged, label_pair_counts, label_pair_counts_ragged  # noqa: F401
+from .label_targets import label_targets_to_masks, panoptic_targets, semantic_targets  # noqa: F401
 from .panoptic_eval import (COCOPanopticEvaluator, PanopticGroundTruth, PQStat, evaluate_panoptic,  # noqa: F401
                             id2rgb, pq_from_counts, rgb2id)
 from .tta import SemanticSegmentorWithTTA, semantic_inference_tta, tta_view_sizes  # noqa: F401

@@ -103,6 +103,9 @@ _SIGNATURES = {
     "m2f_point_loss_chunks": [_i],
     "m2f_point_loss_fwd": [_p, _i, _l, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p],
     "m2f_point_loss_bwd": [_p, _i, _l, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p],
+    "m2f_point_match_cost_labels": [_p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _f, _f, _f, _p, _l, _p, _p],
+    "m2f_point_loss_fwd_labels": [_p, _i, _l, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p],
+    "m2f_point_loss_bwd_labels": [_p, _i, _l, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p],
     "m2f_infer_semantic": [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p],
     "m2f_infer_semantic_tta": [_p, _i, _l, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p],
     "m2f_infer_panoptic_pass": [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p],
@@ -125,6 +128,7 @@ _SIGNATURES = {
     "m2f_bits_pair_counts_ragged": [_p, _l, _p, _i, _p, _l, _p, _l, _p, _l, _l, _p, _p, _p, _p, _l, _p],
     "m2f_label_counts_geometry": [_p, _p, _p, _p],
     "m2f_label_pair_counts_ragged": [_p, _i, _l, _p, _i, _l, _p, _i, _p, _l, _p, _l, _i, _i, _l, _i, _p, _l, _p, _p],
+    "m2f_label_histogram_ragged": [_p, _i, _l, _p, _i, _p, _l, _i, _i, _l, _i, _p, _l, _p, _p],
     "m2f_poly_crossings": [_p, _p, _p, _l, _l, _p, _p],
     "m2f_poly_decode_bits_ragged": [_p, _l, _p, _l, _p, _i, _p, _p, _p, _l, _p, _l, _p],
     "m2f_bits_boundary_tiles": [_p, _p, _p],

@@ -46,6 +46,11 @@
 // The compiler reports 33 to 42 VGPRs, no VGPR spill and no scratch for every instantiation; the LDS ones spill 2 to
 // 4 SGPRs, which go to lanes of a VGPR and cost no memory traffic.
 //
+// Label histograms (m2f_label_histogram_ragged: which classes an image holds and their areas, for the training
+// targets of bm2f_amd/label_targets.py) are the same kernel without the second plane (kPair = false): the table of an
+// image is rows x 1, the column is always 0 and b is neither checked nor read.  Loads, keys of a, wave-merged adds,
+// the LDS copy and the 64-bit counters are shared.
+//
 // The tables live in device memory where the entry point cannot read them, so the kernel checks every field against
 // the sizes passed by value: a malformed table counts nothing or unspecified values, never outside the buffers.
 #include "bm2f.h"
@@ -132,14 +137,15 @@ struct Image {
   bool ok;
 };
 
-__device__ __forceinline__ Image load_image(const int64_t* __restrict__ images, int64_t i, int64_t a_elems,
+// pair: the image has a plane of b to be checked
+__device__ __forceinline__ Image load_image(const int64_t* __restrict__ images, int64_t i, int64_t a_elems, bool pair,
                                             int64_t b_elems, int64_t total_ids, int64_t out_len) {
   const int64_t* d = images + i * kFields;
   Image r;
   r.a_off = d[0], r.b_off = d[1], r.pixels = d[2], r.out_off = d[5], r.id_off = d[6];
   const int64_t rows = d[3], cols = d[4], ids = d[7];
-  r.ok = r.pixels >= 0 && r.a_off >= 0 && r.b_off >= 0 && r.a_off <= a_elems - r.pixels &&
-         r.b_off <= b_elems - r.pixels && rows >= 1 && cols >= 1 && rows <= kIntMax && cols <= kIntMax &&
+  r.ok = r.pixels >= 0 && r.a_off >= 0 && r.a_off <= a_elems - r.pixels &&
+         (!pair || (r.b_off >= 0 && r.b_off <= b_elems - r.pixels)) && (pair || cols == 1) && rows >= 1 && cols >= 1 && rows <= kIntMax && cols <= kIntMax &&
          rows * cols <= kIntMax && r.out_off >= 0 && r.out_off <= out_len - rows * cols &&
          (ids < 0 || (ids <= kMaxIds && ids <= rows - 1 && r.id_off >= 0 && r.id_off <= total_ids - ids));
   r.rows = r.ok ? static_cast<int>(rows) : 1;
@@ -149,8 +155,9 @@ __device__ __forceinline__ Image load_image(const int64_t* __restrict__ images, 
   return r;
 }
 
-// grid (num_blocks): blocks (num_blocks, 2) int32 = (image, chunk of kChunkVecs vectors)
-template <class TA, class TB, bool kLds>
+// grid (num_blocks): blocks (num_blocks, 2) int32 = (image, chunk of kChunkVecs vectors).  !kPair: a histogram of a
+// alone (cols = 1); b is not read.
+template <class TA, class TB, bool kLds, bool kPair = true>
 __global__ void __launch_bounds__(kThreads) count_kernel(const TA* __restrict__ a, int64_t a_elems, int a_wide,
                                                          const TB* __restrict__ b, int64_t b_elems, int b_wide,
                                                          const int64_t* __restrict__ images, int num_images,
@@ -163,13 +170,13 @@ __global__ void __launch_bounds__(kThreads) count_kernel(const TA* __restrict__ 
   const int i = blocks[2 * static_cast<int64_t>(blockIdx.x)];
   const int chunk = blocks[2 * static_cast<int64_t>(blockIdx.x) + 1];
   if (i < 0 || i >= num_images || chunk < 0) return;   // uniform over the workgroup, like every return below
-  const Image im = load_image(images, i, a_elems, b_elems, total_ids, out_len);
+  const Image im = load_image(images, i, a_elems, kPair, b_elems, total_ids, out_len);
   if (!im.ok || (kLds && im.bins > lds_bins)) return;
   const int64_t a0 = im.a_off - im.a_off % kVec;                         // the vector grid: a's element index
   const int64_t nvec = (im.a_off + im.pixels - a0 + kVec - 1) / kVec;
   const int64_t vec0 = static_cast<int64_t>(chunk) * kChunkVecs;
   if (vec0 >= nvec) return;
-  const bool wide_b = b_wide != 0 && (im.b_off - im.a_off) % kVec == 0;
+  const bool wide_b = kPair && b_wide != 0 && (im.b_off - im.a_off) % kVec == 0;
   if (kLds)
     for (int k = threadIdx.x; k < im.bins; k += kThreads) bins[k] = 0u;
   for (int k = threadIdx.x; k < im.ids; k += kThreads) id_list[k] = ids[im.id_off + k];
@@ -187,7 +194,7 @@ __global__ void __launch_bounds__(kThreads) count_kernel(const TA* __restrict__ 
     const int64_t p0 = e0 - im.a_off;                                   // its first pixel, in [-7, pixels + 7]
     int va[kVec], vb[kVec];
     load_vec(a, e0, im.a_off, im.a_off + im.pixels, a_wide != 0, va);
-    load_vec(b, im.b_off + p0, im.b_off, im.b_off + im.pixels, wide_b, vb);
+    if constexpr (kPair) load_vec(b, im.b_off + p0, im.b_off, im.b_off + im.pixels, wide_b, vb);
 #pragma unroll
     for (int k = 0; k < kVec; ++k) {
       const bool live = p0 + k >= 0 && p0 + k < im.pixels;
@@ -205,7 +212,7 @@ __global__ void __launch_bounds__(kThreads) count_kernel(const TA* __restrict__ 
         row = lo < im.ids && id_list[lo] == va[k] ? lo : last_row;
         seen = va[k], seen_row = row, have_seen = true;
       }
-      const int col = vb[k] >= 0 && vb[k] < im.cols ? vb[k] : -1;
+      const int col = !kPair ? 0 : vb[k] >= 0 && vb[k] < im.cols ? vb[k] : -1;
       const bool good = live && row >= 0 && col >= 0;
       nbad += live && !good ? 1 : 0;
       wave_add<kLds>(good ? row * im.cols + col : 0, good, bins, table);
@@ -221,12 +228,12 @@ __global__ void __launch_bounds__(kThreads) count_kernel(const TA* __restrict__ 
   }
 }
 
-template <class TA, class TB>
+template <class TA, class TB, bool kPair = true>
 int launch(const char* fn, bool lds, int lds_bins, unsigned grid, hipStream_t st, const void* a, int64_t a_elems,
            const void* b, int64_t b_elems, const int64_t* images, int num_images, const int32_t* ids,
            int64_t total_ids, const int32_t* blocks, int64_t ignore, int64_t* out, int64_t out_len, int64_t* bad) {
   const int a_wide = m2f::aligned(a, 16) ? 1 : 0, b_wide = m2f::aligned(b, 16) ? 1 : 0;
-  auto* kern = lds ? &count_kernel<TA, TB, true> : &count_kernel<TA, TB, false>;
+  auto* kern = lds ? &count_kernel<TA, TB, true, kPair> : &count_kernel<TA, TB, false, kPair>;
   const int bytes = lds ? lds_bins * 4 : 0;
   if (lds)
     if (const int rc = m2f::set_max_lds(reinterpret_cast<const void*>(kern), kLdsBins * 4, fn)) return rc;
@@ -288,6 +295,39 @@ extern "C" int m2f_label_pair_counts_ragged(const void* a, int a_bytes, int64_t 
       rc = launch<Label<ab.value>, Label<bb.value>>(fn, lds, lds_bins, grid, st, a, a_elems, b, b_elems, images,
                                                     num_images, ids, total_ids, blocks, ign, out, out_len, bad);
     });
+  });
+  return rc;
+}
+
+extern "C" int m2f_label_histogram_ragged(const void* a, int a_bytes, int64_t a_elems, const int64_t* images,
+                                          int num_images, const int32_t* blocks, int64_t num_blocks, int has_ignore,
+                                          int ignore, int64_t max_bins, int path, int64_t* out, int64_t out_len,
+                                          int64_t* bad, void* stream) {
+  const char* fn = "m2f_label_histogram_ragged";
+  if (!images || !out || !bad || (!a && a_elems > 0) || (!blocks && num_blocks > 0))
+    return m2f::fail(M2F_EINVAL, "%s: null pointer", fn);
+  if (num_images <= 0 || a_elems < 0 || num_blocks < 0 || out_len < 0 || max_bins < 1)
+    return m2f::fail(M2F_EINVAL, "%s: sizes must be positive", fn);
+  if (a_bytes != 1 && a_bytes != 2 && a_bytes != 4)
+    return m2f::fail(M2F_EINVAL, "%s: a is 1, 2 or 4 bytes per label, got %d", fn, a_bytes);
+  if (!m2f::aligned(a, a_bytes) || !m2f::aligned(blocks, 4) || !m2f::aligned(images, 8) || !m2f::aligned(out, 8) ||
+      !m2f::aligned(bad, 8))
+    return m2f::fail(M2F_EINVAL, "%s: a buffer is not aligned to its element size", fn);
+  if (path < 0 || path > 2) return m2f::fail(M2F_EINVAL, "%s: path %d is not 0 (auto), 1 (lds) or 2 (global)", fn, path);
+  if (max_bins > kIntMax) return m2f::fail(M2F_EUNSUPPORTED, "%s: a table of more than 2^31 - 1 counters", fn);
+  if (path == 1 && max_bins > kLdsBins)
+    return m2f::fail(M2F_EINVAL, "%s: a table of %lld counters is beyond the %d of the LDS path", fn,
+                     static_cast<long long>(max_bins), kLdsBins);
+  if (num_blocks > kIntMax) return m2f::fail(M2F_EUNSUPPORTED, "%s: more than 2^31 - 1 table rows", fn);
+  if (num_blocks == 0) return m2f::ok();
+  const bool lds = path == 1 || (path == 0 && max_bins <= kLdsBins);
+  const int64_t ign = has_ignore ? static_cast<int64_t>(ignore) : kNoIgnore;
+  const int lds_bins = static_cast<int>(max_bins < kLdsBins ? max_bins : kLdsBins);
+  int rc = M2F_OK;
+  m2f::dispatch_one_of<1, 2, 4>(a_bytes, [&](auto ab) {     // the width was checked above
+    using TA = Label<ab.value>;
+    rc = launch<TA, TA, false>(fn, lds, lds_bins, static_cast<unsigned>(num_blocks), static_cast<hipStream_t>(stream),
+                               a, a_elems, nullptr, 0, images, num_images, nullptr, 0, blocks, ign, out, out_len, bad);
   });
   return rc;
 }

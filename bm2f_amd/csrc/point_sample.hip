@@ -17,6 +17,12 @@
 // per-image / per-row pointer tables; prediction rows are addressed through a plane index table, never through a
 // gathered copy.  Plane offsets are 64-bit; offsets inside a plane are 32-bit (H * W < 2^31 is checked).
 //
+// Label-map targets (the *_labels entry points): an image's G targets are one (Ht, Wt) map of uint8 / int16 / int32
+// labels plus G int32 ids, target g being the set map == ids[g].  The kernels are the dense ones with another target
+// reader (the TR template parameter): the value of a tap is (label == id) ? 1 : 0 where the dense reader converts a
+// plane element, the taps are summed in the same order and a zero-weight tap is skipped alike, so every result is
+// bitwise what the dense uint8 planes map[None] == ids[:, None, None] give.  The planes never exist.
+//
 // Match cost: a workgroup owns one (image, frame, 256-point tile).  Targets are sampled once per 32-target chunk
 // into LDS, predictions per 32-query chunk and 64-point sub-tile; the (Q, G) partials of sum x t and sum sig(x) t
 // are contracted from LDS with fp32 operands and fp64 accumulators, the row sums of softplus(x) / sig(x) and the
@@ -87,21 +93,65 @@ __device__ __forceinline__ float sample_logit(const void* __restrict__ base, int
   return v;
 }
 
+// Target readers.  Dense<TT>: one plane of TT (uint8 or float) per target.  Labels<LT>: one map of LT labels per image,
+// a target is an id.  Table rows (int64):
+//   match   Dense  [plane pointer, G, Ht, Wt]          Labels  [map pointer, G, Ht, Wt, pointer to G int32 ids]
+//   rows    Dense  [plane pointer, Ht, Wt, Hn, Wn]     Labels  [map pointer, id, Ht, Wt, Hn, Wn]
 template <typename TT>
-__device__ __forceinline__ float sample_target(const TT* __restrict__ plane, const Taps& t) {
+struct Dense {
+  using Elem = TT;
+  static constexpr bool kLabels = false;
+  static constexpr int kMatchFields = 4, kRowFields = 5;
+};
+
+template <typename LT>
+struct Labels {
+  using Elem = LT;
+  static constexpr bool kLabels = true;
+  static constexpr int kMatchFields = 5, kRowFields = 6;
+};
+
+// the value of one tap: the plane's element, or whether the map's label is the target's id
+template <class TR>
+__device__ __forceinline__ float tap_value(typename TR::Elem e, int id) {
+  if constexpr (TR::kLabels) return static_cast<int>(e) == id ? 1.f : 0.f;
+  else return static_cast<float>(e);
+}
+
+template <class TR>
+__device__ __forceinline__ float sample_target(const typename TR::Elem* __restrict__ plane, int id, const Taps& t) {
   float v = 0.f;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
-    if (t.w[i] != 0.f) v += static_cast<float>(plane[t.off[i]]) * t.w[i];
+    if (t.w[i] != 0.f) v += tap_value<TR>(plane[t.off[i]], id) * t.w[i];
   return v;
 }
+
+// one row of the loss kernels' target table
+template <class TR>
+struct RowTarget {
+  const typename TR::Elem* plane;
+  int id, Ht, Wt, Hn, Wn;
+  __device__ __forceinline__ explicit RowTarget(const int64_t* __restrict__ tb) {
+    plane = reinterpret_cast<const typename TR::Elem*>(tb[0]);
+    id = TR::kLabels ? static_cast<int>(tb[1]) : 0;
+    const int64_t* s = tb + (TR::kLabels ? 2 : 1);
+    Ht = static_cast<int>(s[0]), Wt = static_cast<int>(s[1]), Hn = static_cast<int>(s[2]), Wn = static_cast<int>(s[3]);
+  }
+  __device__ __forceinline__ bool ok() const { return plane != nullptr && Ht > 0 && Wt > 0; }
+  __device__ __forceinline__ float sample(float ux, float uy) const {
+    return sample_target<TR>(plane, id, make_taps(ux, uy, Hn, Wn, Ht, Wt));
+  }
+};
 
 // ---------------------------------------------------------------------------------------------------------
 // match cost, phase 1: per-tile partials.  Workspace record of (image b, frame t, tile):
 //   [Q*Gm] sum x t | [Q*Gm] sum sig(x) t | [Q] sum softplus(x) | [Q] sum sig(x) | [Gm] sum t
-// Only columns g < G_b are written (and read by phase 2).  tgt (B, 4) int64: plane pointer, G_b, Ht, Wt.
+// Only columns g < G_b are written (and read by phase 2).  tgt (B, TR::kMatchFields) int64, see the readers.
+// Labels: thread tid reads the four corner labels and weights of point k0 + tid once into LDS (8 KiB), whatever G
+// is; a chunk's ids are staged beside them and t[g][p] = sum_i w_i (label_i == id_g) is formed from registers.
 // ---------------------------------------------------------------------------------------------------------
-template <typename TT>
+template <class TR>
 __global__ void __launch_bounds__(NT) match_partial_kernel(const void* __restrict__ masks, int dtype, int Q, int T, int H,
                                                            int W, const float* __restrict__ coords, int K,
                                                            const int64_t* __restrict__ tgt, int Gm,
@@ -109,13 +159,19 @@ __global__ void __launch_bounds__(NT) match_partial_kernel(const void* __restric
   __shared__ float tt[GC][TILE + 1];
   __shared__ float xs[QC][PT + 1], sg[QC][PT + 1];
   __shared__ float rsp[QC], rss[QC], cts[GC];
+  constexpr int kStage = TR::kLabels ? TILE : 1;   // the label reader's per-point corners; unused by the dense one
+  __shared__ float lw[4][kStage];
+  __shared__ int ll[4][kStage], lid[TR::kLabels ? GC : 1];
+  using TT = typename TR::Elem;
   const int tile = blockIdx.x, t = blockIdx.y, b = blockIdx.z;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int64_t* tb = tgt + 4 * static_cast<int64_t>(b);
+  const int64_t* tb = tgt + TR::kMatchFields * static_cast<int64_t>(b);
   const TT* tbase = reinterpret_cast<const TT*>(tb[0]);
   const int G = static_cast<int>(tb[1] < Gm ? tb[1] : Gm);
   const int Ht = static_cast<int>(tb[2]), Wt = static_cast<int>(tb[3]);
   if (G <= 0 || Ht <= 0 || Wt <= 0 || tbase == nullptr) return;
+  const int32_t* ids = TR::kLabels ? reinterpret_cast<const int32_t*>(tb[TR::kMatchFields - 1]) : nullptr;
+  if (TR::kLabels && ids == nullptr) return;
   float* out = ws + (static_cast<int64_t>(b) * T * ntiles + static_cast<int64_t>(t) * ntiles + tile) * rec;
   const int64_t qg = static_cast<int64_t>(Q) * Gm;
   float* o_xt = out;
@@ -128,21 +184,57 @@ __global__ void __launch_bounds__(NT) match_partial_kernel(const void* __restric
   const int k0 = tile * TILE;
   const int qa = (tid >> 4) * 2, ga = tid & 15;   // this thread's 2 x 2 outputs: q in {qa, qa+1}, g in {ga, ga+16}
 
+  if constexpr (TR::kLabels) {   // made visible by the barriers that open the chunk loop (G > 0)
+    const int k = k0 + tid;
+    const bool live = k < K;
+    const Taps tp = make_taps(live ? cb[2 * k] : -4.f, live ? cb[2 * k + 1] : -4.f, Ht, Wt, Ht, Wt);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      lw[i][tid] = tp.w[i];
+      ll[i][tid] = tp.w[i] != 0.f ? static_cast<int>(tbase[tp.off[i]]) : 0;
+    }
+  }
+
   for (int g0 = 0; g0 < G; g0 += GC) {
     __syncthreads();   // the previous chunk's contraction has finished with tt
-    if (tid < GC) cts[tid] = 0.f;
+    if (tid < GC) {
+      cts[tid] = 0.f;
+      if constexpr (TR::kLabels) lid[tid] = g0 + tid < G ? ids[g0 + tid] : 0;
+    }
     __syncthreads();
     for (int s = 0; s < SUB; ++s) {
-      const int k = k0 + s * PT + lane;
-      const bool live = k < K;
-      Taps tp = make_taps(live ? cb[2 * k] : -4.f, live ? cb[2 * k + 1] : -4.f, Ht, Wt, Ht, Wt);
-      for (int gi = wv; gi < GC; gi += NT / 64) {
-        const int g = g0 + gi;
-        float v = 0.f;
-        if (live && g < G) v = sample_target(tbase + (static_cast<int64_t>(g) * T + t) * thw, tp);
-        tt[gi][s * PT + lane] = v;
-        const float sum = wave_sum(v);
-        if (lane == 0) cts[gi] += sum;   // gi belongs to this wave alone
+      if constexpr (TR::kLabels) {
+        int lab[4];
+        float w[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          lab[i] = ll[i][s * PT + lane];
+          w[i] = lw[i][s * PT + lane];   // all 0 for a point beyond K
+        }
+        for (int gi = wv; gi < GC; gi += NT / 64) {
+          float v = 0.f;
+          if (g0 + gi < G) {
+            const int id = lid[gi];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)   // sample_target's order and its skip of zero-weight taps
+              if (w[i] != 0.f) v += (lab[i] == id ? 1.f : 0.f) * w[i];
+          }
+          tt[gi][s * PT + lane] = v;
+          const float sum = wave_sum(v);
+          if (lane == 0) cts[gi] += sum;   // gi belongs to this wave alone
+        }
+      } else {
+        const int k = k0 + s * PT + lane;
+        const bool live = k < K;
+        Taps tp = make_taps(live ? cb[2 * k] : -4.f, live ? cb[2 * k + 1] : -4.f, Ht, Wt, Ht, Wt);
+        for (int gi = wv; gi < GC; gi += NT / 64) {
+          const int g = g0 + gi;
+          float v = 0.f;
+          if (live && g < G) v = sample_target<TR>(tbase + (static_cast<int64_t>(g) * T + t) * thw, 0, tp);
+          tt[gi][s * PT + lane] = v;
+          const float sum = wave_sum(v);
+          if (lane == 0) cts[gi] += sum;   // gi belongs to this wave alone
+        }
       }
     }
     __syncthreads();
@@ -210,9 +302,10 @@ __global__ void __launch_bounds__(NT) match_partial_kernel(const void* __restric
   }
 }
 
-// phase 2: sum the ntot = T * ntiles records of image b in order (fp64) and write the weighted cost.
+// phase 2: sum the ntot = T * ntiles records of image b in order (fp64) and write the weighted cost.  tgt has
+// `fields` int64 per image, of which the first four are read.
 __global__ void __launch_bounds__(NT) match_reduce_kernel(const float* __restrict__ ws, int64_t rec, int ntot, int B, int Q,
-                                                          int Gm, const int64_t* __restrict__ tgt,
+                                                          int Gm, const int64_t* __restrict__ tgt, int fields,
                                                           const float* __restrict__ cost_class, float w_class, float w_mask,
                                                           float w_dice, double n_points, float* __restrict__ cost) {
   const int64_t idx = static_cast<int64_t>(blockIdx.x) * NT + threadIdx.x;
@@ -221,7 +314,7 @@ __global__ void __launch_bounds__(NT) match_reduce_kernel(const float* __restric
   const int b = static_cast<int>(idx / qg);
   const int64_t r = idx - b * qg;
   const int q = static_cast<int>(r / Gm), g = static_cast<int>(r - static_cast<int64_t>(q) * Gm);
-  const int64_t* tb = tgt + 4 * static_cast<int64_t>(b);
+  const int64_t* tb = tgt + fields * static_cast<int64_t>(b);
   if (g >= tb[1] || tb[2] <= 0 || tb[3] <= 0 || tb[0] == 0) {
     cost[idx] = 0.f;
     return;
@@ -261,9 +354,9 @@ __global__ void __launch_bounds__(NT) uncertainty_kernel(const void* __restrict_
   out[idx] = v;
 }
 
-// tgt (R, 5) int64: plane pointer, Ht, Wt, Hn, Wn (the extent the row's coordinates are normalised over).
-// part (R, chunks, 4): sum BCE(x, t), sum sig(x) t, sum sig(x), sum t over the chunk's points.
-template <typename TT>
+// tgt (R, TR::kRowFields) int64: a RowTarget per row; (Hn, Wn) is the extent the row's coordinates are normalised
+// over.  part (R, chunks, 4): sum BCE(x, t), sum sig(x) t, sum sig(x), sum t over the chunk's points.
+template <class TR>
 __global__ void __launch_bounds__(NT) loss_fwd_kernel(const void* __restrict__ masks, int dtype, int64_t n_planes, int H,
                                                       int W, const int64_t* __restrict__ plane,
                                                       const float* __restrict__ coords, int K,
@@ -271,11 +364,8 @@ __global__ void __launch_bounds__(NT) loss_fwd_kernel(const void* __restrict__ m
   __shared__ float red[NT / 64][4];
   const int r = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x;
   const int64_t pl = plane[r];
-  const int64_t* tb = tgt + 5 * static_cast<int64_t>(r);
-  const TT* tplane = reinterpret_cast<const TT*>(tb[0]);
-  const int Ht = static_cast<int>(tb[1]), Wt = static_cast<int>(tb[2]);
-  const int Hn = static_cast<int>(tb[3]), Wn = static_cast<int>(tb[4]);
-  const bool row_ok = pl >= 0 && pl < n_planes && tplane != nullptr && Ht > 0 && Wt > 0;
+  const RowTarget<TR> row(tgt + TR::kRowFields * static_cast<int64_t>(r));
+  const bool row_ok = pl >= 0 && pl < n_planes && row.ok();
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   if (row_ok) {
     const float* cr = coords + static_cast<int64_t>(r) * K * 2;
@@ -285,7 +375,7 @@ __global__ void __launch_bounds__(NT) loss_fwd_kernel(const void* __restrict__ m
       if (k >= K) continue;
       const float ux = cr[2 * k], uy = cr[2 * k + 1];
       const float x = sample_logit(masks, dtype, pl * (static_cast<int64_t>(H) * W), make_taps(ux, uy, H, W, H, W));
-      const float t = sample_target(tplane, make_taps(ux, uy, Hn, Wn, Ht, Wt));
+      const float t = row.sample(ux, uy);
       const float s = sigmoid(x);
       acc[0] += softplus(x) - x * t;
       acc[1] += s * t;
@@ -308,7 +398,7 @@ __global__ void __launch_bounds__(NT) loss_fwd_kernel(const void* __restrict__ m
 
 // grad (n_planes, H, W) fp32, zeroed by the caller, += d/dx of sum_r (g[r,0] BCE_r + g[r,1] A_r + g[r,2] S_r)
 // (A = sum sig t, S = sum sig) through the bilinear weights: fp32 atomics.
-template <typename TT>
+template <class TR>
 __global__ void __launch_bounds__(NT) loss_bwd_kernel(const void* __restrict__ masks, int dtype, int64_t n_planes, int H,
                                                       int W, const int64_t* __restrict__ plane, int R,
                                                       const float* __restrict__ coords, int K,
@@ -318,16 +408,13 @@ __global__ void __launch_bounds__(NT) loss_bwd_kernel(const void* __restrict__ m
   if (idx >= static_cast<int64_t>(R) * K) return;
   const int r = static_cast<int>(idx / K);
   const int64_t pl = plane[r];
-  const int64_t* tb = tgt + 5 * static_cast<int64_t>(r);
-  const TT* tplane = reinterpret_cast<const TT*>(tb[0]);
-  const int Ht = static_cast<int>(tb[1]), Wt = static_cast<int>(tb[2]);
-  const int Hn = static_cast<int>(tb[3]), Wn = static_cast<int>(tb[4]);
-  if (!(pl >= 0 && pl < n_planes && tplane != nullptr && Ht > 0 && Wt > 0)) return;
+  const RowTarget<TR> row(tgt + TR::kRowFields * static_cast<int64_t>(r));
+  if (!(pl >= 0 && pl < n_planes && row.ok())) return;
   const float ux = coords[2 * idx], uy = coords[2 * idx + 1];
   const Taps tp = make_taps(ux, uy, H, W, H, W);
   const int64_t off = pl * (static_cast<int64_t>(H) * W);
   const float x = sample_logit(masks, dtype, off, tp);
-  const float t = sample_target(tplane, make_taps(ux, uy, Hn, Wn, Ht, Wt));
+  const float t = row.sample(ux, uy);
   const float s = sigmoid(x);
   const float dx = g[3 * r] * (s - t) + (g[3 * r + 1] * t + g[3 * r + 2]) * (s * (1.f - s));
 #pragma unroll
@@ -343,9 +430,37 @@ int check_masks(const char* fn, const void* masks, int dtype, int64_t n_planes, 
   return M2F_OK;
 }
 
-int check_tgt_dtype(const char* fn, int tgt_dtype) {
-  if (tgt_dtype != kTgtU8 && tgt_dtype != kTgtF32) return m2f::fail(M2F_EUNSUPPORTED, "%s: target dtype %d", fn, tgt_dtype);
-  return M2F_OK;
+// Target code -> reader: f(Dense<uint8_t> / Dense<float>) for the dense entry points' tgt_dtype, f(Labels<...>) for
+// the label entry points' bytes per label.  false (f not called) for any other code.
+template <typename F>
+bool dispatch_dense(int tgt_dtype, F&& f) {
+  if (tgt_dtype == kTgtU8) f(Dense<uint8_t>{});
+  else if (tgt_dtype == kTgtF32) f(Dense<float>{});
+  else return false;
+  return true;
+}
+
+template <typename F>
+bool dispatch_labels(int label_bytes, F&& f) {
+  if (label_bytes == 1) f(Labels<uint8_t>{});
+  else if (label_bytes == 2) f(Labels<int16_t>{});
+  else if (label_bytes == 4) f(Labels<int32_t>{});
+  else return false;
+  return true;
+}
+
+int bad_target(const char* fn, bool labels, int code) {
+  return m2f::fail(M2F_EUNSUPPORTED, labels ? "%s: %d bytes per label (1, 2 or 4)" : "%s: target dtype %d", fn, code);
+}
+
+// code: tgt_dtype of the dense entry points, bytes per label of the label ones
+template <typename F>
+bool dispatch_target(bool labels, int code, F&& f) {
+  return labels ? dispatch_labels(code, f) : dispatch_dense(code, f);
+}
+
+bool known_target(bool labels, int code) {
+  return dispatch_target(labels, code, [](auto) {});
 }
 
 int64_t match_record(int Q, int Gm) { return 2 * static_cast<int64_t>(Q) * Gm + 2 * static_cast<int64_t>(Q) + Gm; }
@@ -360,14 +475,14 @@ extern "C" int m2f_point_match_workspace(int B, int T, int Q, int Gm, int K, int
   return m2f::ok();
 }
 
-extern "C" int m2f_point_match_cost(const void* masks, int dtype, int B, int Q, int T, int H, int W, const float* coords,
-                                    int K, const int64_t* tgt, int tgt_dtype, int Gm, const float* cost_class,
-                                    float w_class, float w_mask, float w_dice, float* workspace, int64_t ws_floats,
-                                    float* cost, void* stream) {
-  const char* fn = "m2f_point_match_cost";
+namespace {
+
+int match_cost(const char* fn, bool labels, const void* masks, int dtype, int B, int Q, int T, int H, int W,
+               const float* coords, int K, const int64_t* tgt, int code, int Gm, const float* cost_class, float w_class,
+               float w_mask, float w_dice, float* workspace, int64_t ws_floats, float* cost, void* stream) {
   if (B < 0 || Q < 0 || T < 1 || K < 1 || Gm < 0) return m2f::fail(M2F_EINVAL, "%s: bad sizes", fn);
   if (int e = check_masks(fn, masks, dtype, static_cast<int64_t>(B) * Q * T, H, W)) return e;
-  if (int e = check_tgt_dtype(fn, tgt_dtype)) return e;
+  if (!known_target(labels, code)) return bad_target(fn, labels, code);
   if (B == 0 || Q == 0 || Gm == 0) return m2f::ok();
   if (!coords || !tgt || !workspace || !cost) return m2f::fail(M2F_EINVAL, "%s: null argument", fn);
   if (B > 65535 || T > 65535) return m2f::fail(M2F_EUNSUPPORTED, "%s: B or T > 65535", fn);
@@ -378,14 +493,71 @@ extern "C" int m2f_point_match_cost(const void* masks, int dtype, int B, int Q, 
     return m2f::fail(M2F_EUNSUPPORTED, "%s: problem too large", fn);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(ntiles, T, B);
-  if (tgt_dtype == kTgtU8)
-    match_partial_kernel<uint8_t><<<grid, NT, 0, st>>>(masks, dtype, Q, T, H, W, coords, K, tgt, Gm, workspace, rec, ntiles);
-  else
-    match_partial_kernel<float><<<grid, NT, 0, st>>>(masks, dtype, Q, T, H, W, coords, K, tgt, Gm, workspace, rec, ntiles);
+  int fields = 0;
+  dispatch_target(labels, code, [&](auto tr) {
+    using TR = decltype(tr);
+    fields = TR::kMatchFields;
+    match_partial_kernel<TR><<<grid, NT, 0, st>>>(masks, dtype, Q, T, H, W, coords, K, tgt, Gm, workspace, rec, ntiles);
+  });
   if (int e = m2f::check_launch(fn)) return e;
   match_reduce_kernel<<<m2f::ceil_div(static_cast<int64_t>(B) * Q * Gm, NT), NT, 0, st>>>(
-      workspace, rec, T * ntiles, B, Q, Gm, tgt, cost_class, w_class, w_mask, w_dice, static_cast<double>(T) * K, cost);
+      workspace, rec, T * ntiles, B, Q, Gm, tgt, fields, cost_class, w_class, w_mask, w_dice, static_cast<double>(T) * K,
+      cost);
   return m2f::check_launch(fn);
+}
+
+int loss_fwd(const char* fn, bool labels, const void* masks, int dtype, int64_t n_planes, int H, int W,
+             const int64_t* plane, int R, const float* coords, int K, const int64_t* tgt, int code, float* part,
+             void* stream) {
+  if (R < 0 || K < 0) return m2f::fail(M2F_EINVAL, "%s: negative size", fn);
+  if (int e = check_masks(fn, masks, dtype, n_planes, H, W)) return e;
+  if (!known_target(labels, code)) return bad_target(fn, labels, code);
+  if (R == 0 || K == 0) return m2f::ok();
+  if (!plane || !coords || !tgt || !part) return m2f::fail(M2F_EINVAL, "%s: null argument", fn);
+  const int chunks = m2f_point_loss_chunks(K);
+  if (chunks > 65535) return m2f::fail(M2F_EUNSUPPORTED, "%s: K too large", fn);
+  const dim3 grid(R, chunks);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  dispatch_target(labels, code, [&](auto tr) {
+    loss_fwd_kernel<decltype(tr)><<<grid, NT, 0, st>>>(masks, dtype, n_planes, H, W, plane, coords, K, tgt, part);
+  });
+  return m2f::check_launch(fn);
+}
+
+int loss_bwd(const char* fn, bool labels, const void* masks, int dtype, int64_t n_planes, int H, int W,
+             const int64_t* plane, int R, const float* coords, int K, const int64_t* tgt, int code,
+             const float* grad_rows, float* grad, void* stream) {
+  if (R < 0 || K < 0) return m2f::fail(M2F_EINVAL, "%s: negative size", fn);
+  if (int e = check_masks(fn, masks, dtype, n_planes, H, W)) return e;
+  if (!known_target(labels, code)) return bad_target(fn, labels, code);
+  if (R == 0 || K == 0) return m2f::ok();
+  if (!plane || !coords || !tgt || !grad_rows || !grad) return m2f::fail(M2F_EINVAL, "%s: null argument", fn);
+  const int64_t n = static_cast<int64_t>(R) * K;
+  if (n > (static_cast<int64_t>(INT32_MAX) - NT) * NT) return m2f::fail(M2F_EUNSUPPORTED, "%s: problem too large", fn);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  dispatch_target(labels, code, [&](auto tr) {
+    loss_bwd_kernel<decltype(tr)><<<m2f::ceil_div(n, NT), NT, 0, st>>>(masks, dtype, n_planes, H, W, plane, R, coords, K,
+                                                                       tgt, grad_rows, grad);
+  });
+  return m2f::check_launch(fn);
+}
+
+}  // namespace
+
+extern "C" int m2f_point_match_cost(const void* masks, int dtype, int B, int Q, int T, int H, int W, const float* coords,
+                                    int K, const int64_t* tgt, int tgt_dtype, int Gm, const float* cost_class,
+                                    float w_class, float w_mask, float w_dice, float* workspace, int64_t ws_floats,
+                                    float* cost, void* stream) {
+  return match_cost("m2f_point_match_cost", false, masks, dtype, B, Q, T, H, W, coords, K, tgt, tgt_dtype, Gm, cost_class,
+                    w_class, w_mask, w_dice, workspace, ws_floats, cost, stream);
+}
+
+extern "C" int m2f_point_match_cost_labels(const void* masks, int dtype, int B, int Q, int H, int W, const float* coords,
+                                           int K, const int64_t* tgt, int label_bytes, int Gm, const float* cost_class,
+                                           float w_class, float w_mask, float w_dice, float* workspace,
+                                           int64_t ws_floats, float* cost, void* stream) {
+  return match_cost("m2f_point_match_cost_labels", true, masks, dtype, B, Q, 1, H, W, coords, K, tgt, label_bytes, Gm,
+                    cost_class, w_class, w_mask, w_dice, workspace, ws_floats, cost, stream);
 }
 
 extern "C" int m2f_point_uncertainty(const void* masks, int dtype, int64_t n_planes, int H, int W, const int64_t* plane,
@@ -407,40 +579,27 @@ extern "C" int m2f_point_loss_chunks(int K) { return K > 0 ? static_cast<int>(m2
 extern "C" int m2f_point_loss_fwd(const void* masks, int dtype, int64_t n_planes, int H, int W, const int64_t* plane, int R,
                                   const float* coords, int K, const int64_t* tgt, int tgt_dtype, float* part,
                                   void* stream) {
-  const char* fn = "m2f_point_loss_fwd";
-  if (R < 0 || K < 0) return m2f::fail(M2F_EINVAL, "%s: negative size", fn);
-  if (int e = check_masks(fn, masks, dtype, n_planes, H, W)) return e;
-  if (int e = check_tgt_dtype(fn, tgt_dtype)) return e;
-  if (R == 0 || K == 0) return m2f::ok();
-  if (!plane || !coords || !tgt || !part) return m2f::fail(M2F_EINVAL, "%s: null argument", fn);
-  const int chunks = m2f_point_loss_chunks(K);
-  if (chunks > 65535) return m2f::fail(M2F_EUNSUPPORTED, "%s: K too large", fn);
-  const dim3 grid(R, chunks);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (tgt_dtype == kTgtU8)
-    loss_fwd_kernel<uint8_t><<<grid, NT, 0, st>>>(masks, dtype, n_planes, H, W, plane, coords, K, tgt, part);
-  else
-    loss_fwd_kernel<float><<<grid, NT, 0, st>>>(masks, dtype, n_planes, H, W, plane, coords, K, tgt, part);
-  return m2f::check_launch(fn);
+  return loss_fwd("m2f_point_loss_fwd", false, masks, dtype, n_planes, H, W, plane, R, coords, K, tgt, tgt_dtype, part,
+                  stream);
+}
+
+extern "C" int m2f_point_loss_fwd_labels(const void* masks, int dtype, int64_t n_planes, int H, int W,
+                                         const int64_t* plane, int R, const float* coords, int K, const int64_t* tgt,
+                                         int label_bytes, float* part, void* stream) {
+  return loss_fwd("m2f_point_loss_fwd_labels", true, masks, dtype, n_planes, H, W, plane, R, coords, K, tgt, label_bytes,
+                  part, stream);
 }
 
 extern "C" int m2f_point_loss_bwd(const void* masks, int dtype, int64_t n_planes, int H, int W, const int64_t* plane, int R,
                                   const float* coords, int K, const int64_t* tgt, int tgt_dtype, const float* grad_rows,
                                   float* grad, void* stream) {
-  const char* fn = "m2f_point_loss_bwd";
-  if (R < 0 || K < 0) return m2f::fail(M2F_EINVAL, "%s: negative size", fn);
-  if (int e = check_masks(fn, masks, dtype, n_planes, H, W)) return e;
-  if (int e = check_tgt_dtype(fn, tgt_dtype)) return e;
-  if (R == 0 || K == 0) return m2f::ok();
-  if (!plane || !coords || !tgt || !grad_rows || !grad) return m2f::fail(M2F_EINVAL, "%s: null argument", fn);
-  const int64_t n = static_cast<int64_t>(R) * K;
-  if (n > (static_cast<int64_t>(INT32_MAX) - NT) * NT) return m2f::fail(M2F_EUNSUPPORTED, "%s: problem too large", fn);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (tgt_dtype == kTgtU8)
-    loss_bwd_kernel<uint8_t><<<m2f::ceil_div(n, NT), NT, 0, st>>>(masks, dtype, n_planes, H, W, plane, R, coords, K, tgt,
-                                                                 grad_rows, grad);
-  else
-    loss_bwd_kernel<float><<<m2f::ceil_div(n, NT), NT, 0, st>>>(masks, dtype, n_planes, H, W, plane, R, coords, K, tgt,
-                                                               grad_rows, grad);
-  return m2f::check_launch(fn);
+  return loss_bwd("m2f_point_loss_bwd", false, masks, dtype, n_planes, H, W, plane, R, coords, K, tgt, tgt_dtype,
+                  grad_rows, grad, stream);
+}
+
+extern "C" int m2f_point_loss_bwd_labels(const void* masks, int dtype, int64_t n_planes, int H, int W,
+                                         const int64_t* plane, int R, const float* coords, int K, const int64_t* tgt,
+                                         int label_bytes, const float* grad_rows, float* grad, void* stream) {
+  return loss_bwd("m2f_point_loss_bwd_labels", true, masks, dtype, n_planes, H, W, plane, R, coords, K, tgt, label_bytes,
+                  grad_rows, grad, stream);
 }

@@ -8,6 +8,8 @@ map read back from PNG files).
                                   ``m2f_label_pair_counts_ragged`` (``csrc/label_counts.hip``) and one copy of the
                                   tables to the host.
 :func:`label_pair_counts`         the single-image form.
+:func:`label_histogram_ragged`    the counts of one plane alone, per image (``m2f_label_histogram_ragged``, the same
+                                  kernel without the plane ``b``): which classes an image holds and their areas.
 
 The row of a value ``v`` of ``a``:
 
@@ -279,3 +281,67 @@ def label_pair_counts(a, b, *, rows, cols, ignore=None, ids=None, path="auto"):
     tables, bad = label_pair_counts_ragged([a], [b], rows=rows, cols=cols, ignore=ignore,
                                            ids=None if ids is None else [ids], path=path)
     return tables[0], int(bad[0])
+
+
+def label_histogram_ragged(planes, bins, ignore=None, *, path="auto"):
+    """planes: one label plane per image (uint8, int16 or int32, one dtype for the batch; any shape, read flat, may be
+    empty).  -> ``(counts, bad)`` on the host: ``counts`` (B, bins + 1) int64, column ``v < bins`` the pixels of value
+    ``v`` and column ``bins`` the pixels equal to ``ignore`` (0 without one; ``ignore`` is tested first); ``bad`` (B,)
+    int64, the pixels that are neither.
+
+    If any plane is a HIP tensor: one upload of the small tables, one launch of ``m2f_label_histogram_ragged`` over
+    the whole batch and one copy to the host, planes read in place as by :func:`label_pair_counts_ragged` (``path``
+    as there).  With only host planes the numpy definition (``np.bincount``) runs."""
+    planes = list(planes)
+    B, bins = len(planes), int(bins)
+    if path not in _PATHS:
+        raise ValueError(f"path {path!r} is not one of {sorted(_PATHS)}")
+    if not 1 <= bins < _INT_MAX:
+        raise ValueError("bins must be positive and bins + 1 fit 31 bits")
+    if ignore is not None and not -2 ** 31 <= int(ignore) < 2 ** 31:
+        raise ValueError("ignore must fit an int32")
+    rows = bins + 1
+    dt, devices = None, set()
+    for i, p in enumerate(planes):
+        d = _np_dtype(p)
+        if d not in _A_DTYPES or (dt is not None and d != dt):
+            raise ValueError(f"image {i}: planes must be uint8, int16 or int32, one dtype per batch, got {d}"
+                             + (f" after {dt}" if dt is not None else ""))
+        dt = d
+        if torch.is_tensor(p) and p.device.type == "cuda":
+            devices.add(str(p.device))
+    if len(devices) > 1:
+        raise ValueError(f"planes on several devices: {sorted(devices)}")
+    if B == 0:
+        return np.zeros((0, rows), np.int64), np.zeros(0, np.int64)
+    if not devices:
+        counts, bad = np.zeros((B, rows), np.int64), np.zeros(B, np.int64)
+        for i, p in enumerate(planes):
+            a = _host(p).astype(np.int64)
+            row = np.where((a >= 0) & (a < bins), a, -1)
+            if ignore is not None:
+                row = np.where(a == int(ignore), bins, row)
+            bad[i] = int((row < 0).sum())
+            counts[i] = np.bincount(row[row >= 0], minlength=rows)
+        return counts, bad
+    device = torch.device(devices.pop())
+    vec, _, lds_bins, _ = geometry()
+    if path == "lds" and rows > lds_bins:
+        raise ValueError(f"path='lds': a table of {rows} counters is beyond the {lds_bins} the LDS path holds")
+    with torch.cuda.device(device):
+        base, off, elems, keep = _gather(planes, dt, device, 2 * vec)
+        pixels = np.array([p.numel() if torch.is_tensor(p) else np.asarray(p).size for p in planes], dtype=np.int64)
+        one, none = np.ones(B, np.int64), np.zeros(B, np.int64)
+        images = np.stack((off, none, pixels, rows * one, one, rows * np.arange(B, dtype=np.int64), none, -one),
+                          axis=1).astype(np.int64)
+        assert images.shape[1] == _FIELDS
+        blocks = _blocks(off, pixels)
+        dev = _upload({"images": images, "blocks": blocks}, device)                              # one copy
+        out = torch.zeros(B * rows + B, dtype=torch.int64, device=device)
+        _native.call("m2f_label_histogram_ragged", base or None, dt.itemsize, elems, dev["images"].data_ptr(), B,
+                     _native.ptr_or_null(dev["blocks"]), blocks.shape[0], int(ignore is not None), int(ignore or 0),
+                     rows, _PATHS[path], out.data_ptr(), B * rows, out.data_ptr() + 8 * B * rows,
+                     _native.stream(device))
+        host = out.cpu().numpy()                                                                  # the one copy
+    del keep
+    return host[:B * rows].reshape(B, rows).copy(), host[B * rows:].copy()

@@ -7,7 +7,9 @@ Drop-ins for the reference's ``HungarianMatcher`` (mask2former/modeling/matcher.
 ``loss_mask``, ``loss_dice`` and the ``_i`` aux copies).  Inputs as in the reference: ``pred_logits`` (B, Q, C+1),
 ``pred_masks`` (B, Q, H, W) or (B, Q, T, H, W) in fp32 / fp16 / bf16 (evaluated in fp32); target dicts with
 ``labels`` and ``masks`` (G, Ht, Wt) / (G, T, Ht, Wt) (bool, uint8 or float, at their own resolution), and
-``box_masks_full`` for ``mask_target_type="box_mask"``.
+``box_masks_full`` for ``mask_target_type="box_mask"``.  The image classes also take label-map targets
+(``bm2f_amd/label_targets.py``): ``labels``, ``label_map`` (Ht, Wt) and ``ids`` (G,) in place of ``masks``, target g
+being ``label_map == ids[g]``; a batch is all dense or all label maps.
 
 Semantics (``point_sample(x, u) = grid_sample(x, 2u - 1, bilinear, zeros, align_corners=False)``):
 
@@ -28,7 +30,9 @@ Where the work runs on a HIP device (csrc/point_sample.hip): the matching cost o
 the oversampling pass is ``m2f_point_uncertainty`` + ``torch.topk``; the losses are the ``m2f_point_loss_fwd`` /
 ``_bwd`` pair, which reads predictions through a plane index table and targets in place through a pointer table
 (no gathered ``pred_masks[src_idx]``, no float copy of the targets) and scatters the gradient with fp32 atomics into
-one dense buffer per head.  ``num_masks`` stays a device scalar under torch.distributed; matcher status is checked
+one dense buffer per head.  Label-map targets take the ``_labels`` twins of the match-cost and loss entry points,
+which read the map and the ids in place and give bitwise the dense uint8 planes' results; no plane is formed.
+``num_masks`` stays a device scalar under torch.distributed; matcher status is checked
 with one sync per criterion call (``check_matching = False`` skips it).  Indices are int64 tensors on the masks'
 device.
 
@@ -49,6 +53,7 @@ from torch.autograd import Function
 
 from . import _native
 from . import weaksup as ws
+from .label_targets import as_label_maps, label_targets_to_masks
 from .set_criterion import _class_cost, _Matcher, _SetCriterion, _Targets
 
 
@@ -82,10 +87,18 @@ class MaskTargets(_Targets):
     def planes(self, key="masks"):
         """dict: ``list`` per-image planes (G, [T,] Ht, Wt), ``code`` 0 uint8 / 1 fp32, ``sizes`` (Ht, Wt) per
         image, ``pad`` the batch maximum, and on a HIP device ``match`` (B, 4) int64 [pointer, G, Ht, Wt] and
-        ``rows`` (B, 4) int64 [pointer, plane bytes, Ht, Wt]."""
+        ``rows`` (B, 4) int64 [pointer, plane bytes, Ht, Wt].
+
+        Label-map targets under ``"masks"``: on a HIP device ``code`` 2, ``list`` the maps (Ht, Wt), ``label_bytes``
+        their item size, ``ids`` the batch's ids (sum G,) int32, ``match`` (B, 5) [map pointer, G, Ht, Wt, pointer
+        to the image's ids] and ``rows`` (B, 5) [map pointer, 0, Ht, Wt, offset of the image's ids]; on the CPU the
+        dense uint8 planes made from the maps."""
         hit = self._planes.get(key)
         if hit is not None:
             return hit
+        if key == "masks" and any("label_map" in t for t in self._targets):
+            out = self._planes[key] = self._label_planes()
+            return out
         raw = [t[key].to(self.device) for t in self._targets]
         nd = 4 if self.video else 3
         for b, m in enumerate(raw):
@@ -112,13 +125,42 @@ class MaskTargets(_Targets):
         self._planes[key] = out
         return out
 
+    def _label_planes(self):
+        if self.video:
+            raise ValueError("label-map targets are for images; the video classes take dense masks")
+        for b, t in enumerate(self._targets):
+            if "label_map" not in t or "masks" in t:
+                raise ValueError(f"targets[{b}]: a batch is either all dense masks or all label maps")
+            if "ids" not in t or t["ids"].dim() != 1 or t["ids"].shape[0] != self.G[b]:
+                raise ValueError(f"targets[{b}]['ids'] must be (G,) with one id per label")
+        if not self.cuda:
+            dense = [label_targets_to_masks(t).view(torch.uint8) for t in self._targets]
+            sizes = [(int(m.shape[-2]), int(m.shape[-1])) for m in dense]
+            return {"list": dense, "code": 0, "sizes": sizes,
+                    "pad": (max((s[0] for s in sizes), default=0), max((s[1] for s in sizes), default=0))}
+        maps = as_label_maps([t["label_map"].to(self.device) for t in self._targets])
+        ids = torch.cat([t["ids"].to(self.device, torch.int32) for t in self._targets]) if self.B else None
+        sizes = [(int(m.shape[0]), int(m.shape[1])) for m in maps]
+        item = maps[0].element_size() if maps else 1
+        # an image without targets or pixels has nothing to point at: null pointer, skipped by the kernels
+        ptr = [m.data_ptr() if m.numel() and self.G[b] else 0 for b, m in enumerate(maps)]
+        id_ptr = [ids.data_ptr() + 4 * self.offsets[b] if self.G[b] else 0 for b in range(self.B)]
+        return {"list": maps, "code": 2, "label_bytes": item, "ids": ids, "sizes": sizes,
+                "pad": (max((s[0] for s in sizes), default=0), max((s[1] for s in sizes), default=0)),
+                "match": ws.h2d([v for b in range(self.B) for v in (ptr[b], self.G[b], *sizes[b], id_ptr[b])],
+                                self.device, torch.int64).view(self.B, 5),
+                "rows": ws.h2d([v for b in range(self.B) for v in (ptr[b], 0, *sizes[b], self.offsets[b])],
+                               self.device, torch.int64).view(self.B, 5)}
+
 
 # ------------------------------------------------------------------------------------------------------------
 # kernels
 # ------------------------------------------------------------------------------------------------------------
-def match_cost(masks, coords, tgt_table, tgt_code, Gm, cost_class=None, w_class=0.0, w_mask=1.0, w_dice=1.0):
+def match_cost(masks, coords, tgt_table, tgt_code, Gm, cost_class=None, w_class=0.0, w_mask=1.0, w_dice=1.0,
+               label_bytes=0):
     """``m2f_point_match_cost``: masks (B, Q, H, W) or (B, Q, T, H, W), coords (B, K, 2) fp32, tgt_table (B, 4)
-    int64 -> (B, Q, Gm) fp32 weighted cost.  The caller keeps the target tensors alive."""
+    int64 -> (B, Q, Gm) fp32 weighted cost.  ``tgt_code`` 2: label-map targets of ``label_bytes`` per label through
+    ``m2f_point_match_cost_labels`` (images only, tgt_table (B, 5)).  The caller keeps the target tensors alive."""
     ws._need_cuda(masks, coords, tgt_table, cost_class)
     x = _logit_tensor(masks)
     B, Q = x.shape[:2]
@@ -126,8 +168,11 @@ def match_cost(masks, coords, tgt_table, tgt_code, Gm, cost_class=None, w_class=
     H, W = x.shape[-2:]
     K = coords.shape[1]
     c = coords.to(torch.float32).contiguous()
-    if c.shape != (B, K, 2) or tgt_table.shape != (B, 4) or tgt_table.dtype != torch.int64:
-        raise ValueError("coords must be (B, K, 2) and the target table (B, 4) int64")
+    labels = tgt_code == 2
+    if labels and x.dim() == 5:
+        raise ValueError("label-map targets are for images")
+    if c.shape != (B, K, 2) or tgt_table.shape != (B, 5 if labels else 4) or tgt_table.dtype != torch.int64:
+        raise ValueError("coords must be (B, K, 2) and the target table (B, 4) int64, (B, 5) for label maps")
     cc = None
     if cost_class is not None:
         cc = cost_class.to(torch.float32).contiguous()
@@ -136,9 +181,14 @@ def match_cost(masks, coords, tgt_table, tgt_code, Gm, cost_class=None, w_class=
     n = _native.query("m2f_point_match_workspace", B, T, Q, Gm, K)
     work = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
     cost = torch.empty((B, Q, Gm), dtype=torch.float32, device=x.device)
-    _native.call("m2f_point_match_cost", x.data_ptr(), _native.dtype_code(x.dtype, "mask criterion"), B, Q, T, H, W,
-                 c.data_ptr(), K, tgt_table.contiguous().data_ptr(), tgt_code, Gm, _native.ptr(cc), w_class, w_mask,
-                 w_dice, work.data_ptr(), n, cost.data_ptr(), _native.stream(x))
+    tail = (Gm, _native.ptr(cc), w_class, w_mask, w_dice, work.data_ptr(), n, cost.data_ptr(), _native.stream(x))
+    dt = _native.dtype_code(x.dtype, "mask criterion")
+    if labels:
+        _native.call("m2f_point_match_cost_labels", x.data_ptr(), dt, B, Q, H, W, c.data_ptr(), K,
+                     tgt_table.contiguous().data_ptr(), label_bytes, *tail)
+    else:
+        _native.call("m2f_point_match_cost", x.data_ptr(), dt, B, Q, T, H, W, c.data_ptr(), K,
+                     tgt_table.contiguous().data_ptr(), tgt_code, *tail)
     return cost
 
 
@@ -159,22 +209,24 @@ def point_uncertainty(masks, plane, coords):
 
 class PointLossSums(Function):
     """Per row r: sum_k BCE(x, t), sum sig(x) t, sum sig(x), sum t at the row's K points; x sampled from plane
-    ``plane[r]`` of masks, t from the row's target (tgt_rows (R, 5) int64: pointer, Ht, Wt, Hn, Wn).  Differentiable
+    ``plane[r]`` of masks, t from the row's target (tgt_rows (R, 5) int64: pointer, Ht, Wt, Hn, Wn; for label-map
+    targets, ``tgt_code`` 2, (R, 6): map pointer, id, Ht, Wt, Hn, Wn and ``label_bytes`` per label).  Differentiable
     in masks: the backward pass re-samples (only the tables and coordinates are saved) and scatters with fp32
     atomics into one dense gradient."""
 
     @staticmethod
-    def forward(ctx, masks, plane, coords, tgt_rows, tgt_code, keep):
+    def forward(ctx, masks, plane, coords, tgt_rows, tgt_code, keep, label_bytes=0):
         H, W = masks.shape[-2:]
         R, K = coords.shape[:2]
         chunks = _native.load().m2f_point_loss_chunks(K)
         part = torch.empty((R, max(chunks, 1), 4), dtype=torch.float32, device=masks.device)
         n_planes = masks.numel() // (H * W)
-        _native.call("m2f_point_loss_fwd", masks.data_ptr(), _native.dtype_code(masks.dtype, "mask criterion"),
-                     n_planes, H, W, plane.data_ptr(), R, coords.data_ptr(), K, tgt_rows.data_ptr(), tgt_code,
-                     part.data_ptr(), _native.stream(masks))
+        # (entry point suffix, its target code): the dense dtype code, or the bytes per label
+        ctx.target = ("_labels", label_bytes) if tgt_code == 2 else ("", tgt_code)
+        _native.call("m2f_point_loss_fwd" + ctx.target[0], masks.data_ptr(),
+                     _native.dtype_code(masks.dtype, "mask criterion"), n_planes, H, W, plane.data_ptr(), R,
+                     coords.data_ptr(), K, tgt_rows.data_ptr(), ctx.target[1], part.data_ptr(), _native.stream(masks))
         ctx.save_for_backward(masks, plane, coords, tgt_rows)
-        ctx.tgt_code = tgt_code
         ctx.keep = keep                      # the target tensors the pointer table refers to
         sums = part.sum(1)
         bce, inter, sig, tsum = sums.unbind(1)
@@ -188,18 +240,20 @@ class PointLossSums(Function):
         R, K = coords.shape[:2]
         g = torch.stack([g_bce, g_inter, g_sig], 1).to(torch.float32).contiguous()
         grad = torch.zeros(masks.shape, dtype=torch.float32, device=masks.device)
-        _native.call("m2f_point_loss_bwd", masks.data_ptr(), _native.dtype_code(masks.dtype, "mask criterion"),
-                     grad.numel() // (H * W), H, W, plane.data_ptr(), R, coords.data_ptr(), K, tgt_rows.data_ptr(),
-                     ctx.tgt_code, g.data_ptr(), grad.data_ptr(), _native.stream(masks))
-        return grad.to(masks.dtype), None, None, None, None, None
+        _native.call("m2f_point_loss_bwd" + ctx.target[0], masks.data_ptr(),
+                     _native.dtype_code(masks.dtype, "mask criterion"), grad.numel() // (H * W), H, W, plane.data_ptr(),
+                     R, coords.data_ptr(), K, tgt_rows.data_ptr(), ctx.target[1], g.data_ptr(), grad.data_ptr(),
+                     _native.stream(masks))
+        return grad.to(masks.dtype), None, None, None, None, None, None
 
 
-def point_loss_sums(masks, plane, coords, tgt_rows, tgt_code, keep=None):
+def point_loss_sums(masks, plane, coords, tgt_rows, tgt_code, keep=None, label_bytes=0):
     ws._need_cuda(masks, plane, coords, tgt_rows)
-    if tgt_rows.dtype != torch.int64 or tgt_rows.shape != (coords.shape[0], 5) or plane.dtype != torch.int64:
-        raise ValueError("plane must be (R,) int64 and the target table (R, 5) int64")
+    fields = 6 if tgt_code == 2 else 5
+    if tgt_rows.dtype != torch.int64 or tgt_rows.shape != (coords.shape[0], fields) or plane.dtype != torch.int64:
+        raise ValueError("plane must be (R,) int64 and the target table (R, 5) int64, (R, 6) for label maps")
     return PointLossSums.apply(_logit_tensor(masks), plane.contiguous(), coords.to(torch.float32).contiguous(),
-                               tgt_rows.contiguous(), tgt_code, keep)
+                               tgt_rows.contiguous(), tgt_code, keep, label_bytes)
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -229,7 +283,7 @@ class HungarianMatcher(_Matcher):
         c_class = _class_cost(logits, tg.labels_padded())
         if tg.cuda:
             return match_cost(masks, coords, pl["match"], pl["code"], Gm, c_class, self.cost_class, self.cost_mask,
-                              self.cost_dice)
+                              self.cost_dice, label_bytes=pl.get("label_bytes", 0))
         C = torch.zeros((B, Q, Gm), dtype=torch.float32)
         for b in range(B):
             G = tg.G[b]
@@ -332,10 +386,15 @@ class SetCriterion(_SetCriterion):
             # the image criterion samples targets zero-padded to the batch maximum; video clips share one size
             norm = size if self._video else torch.tensor(pl["pad"], dtype=torch.int64).pin_memory().to(
                 dev, non_blocking=True).expand(N, T, 2)
-            rows = torch.cat([ptr[:, :, None], size, norm], 2).reshape(N * T, 5)
+            cols = [ptr[:, :, None], size, norm]
+            if pl["code"] == 2:   # every row of an image points at its map; the row's target is its id
+                cols.insert(1, pl["ids"][info[:, 4] + tgt_idx].long()[:, None, None])
+            rows = torch.cat(cols, 2).reshape(N * T, len(cols) + 2)
             with torch.no_grad():
                 coords = self._sample_points(lambda u: point_uncertainty(x.detach(), plane, u), N * T, dev)
-            bce, inter, sig, tsum = point_loss_sums(x, plane, coords, rows, pl["code"], keep=pl["list"])
+            bce, inter, sig, tsum = point_loss_sums(x, plane, coords, rows, pl["code"],
+                                                    keep=(pl["list"], pl.get("ids")),
+                                                    label_bytes=pl.get("label_bytes", 0))
         else:
             src = masks[batch_idx, src_idx].float()
             Hp, Wp = pl["pad"]

@@ -564,6 +564,25 @@ int m2f_point_loss_fwd(const void* masks, int dtype, int64_t n_planes, int H, in
 int m2f_point_loss_bwd(const void* masks, int dtype, int64_t n_planes, int H, int W, const int64_t* plane, int R,
                        const float* coords, int K, const int64_t* tgt, int tgt_dtype, const float* grad_rows,
                        float* grad, void* stream);
+/* The same three on label-map targets: the G_b targets of image b are one (Ht, Wt) map of labels (label_bytes
+ * 1 = uint8, 2 = int16, 4 = int32) and G_b int32 ids, target g being the set map == ids[g].  The value of a tap
+ * is (label == id) ? 1 : 0, summed in the dense kernels' order, so every output is bitwise what the dense uint8
+ * planes map[None] == ids[:, None, None] give through the entry points above; those planes are never formed.
+ *   m2f_point_match_cost_labels  images only (T = 1; workspace from m2f_point_match_workspace with T = 1).
+ *       tgt (B, 5) int64 [map pointer, G_b, Ht, Wt, pointer to the G_b ids].  A workgroup reads the four corner
+ *       labels of each of its points once, whatever G_b is.
+ *   m2f_point_loss_fwd_labels / _bwd_labels  tgt (R, 6) int64 [map pointer, id, Ht, Wt, Hn, Wn].  A corner beyond
+ *       the map contributes 0, as does a pixel whose label is no id (ignored / VOID). */
+int m2f_point_match_cost_labels(const void* masks, int dtype, int B, int Q, int H, int W, const float* coords, int K,
+                                const int64_t* tgt, int label_bytes, int Gm, const float* cost_class,
+                                float w_class, float w_mask, float w_dice, float* workspace, int64_t ws_floats,
+                                float* cost, void* stream);
+int m2f_point_loss_fwd_labels(const void* masks, int dtype, int64_t n_planes, int H, int W, const int64_t* plane,
+                              int R, const float* coords, int K, const int64_t* tgt, int label_bytes, float* part,
+                              void* stream);
+int m2f_point_loss_bwd_labels(const void* masks, int dtype, int64_t n_planes, int H, int W, const int64_t* plane,
+                              int R, const float* coords, int K, const int64_t* tgt, int label_bytes,
+                              const float* grad_rows, float* grad, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Inference heads: the eval branch of MaskFormer.forward (maskformer_model.py:333-377) from the
@@ -850,6 +869,15 @@ int m2f_label_pair_counts_ragged(const void* a, int a_bytes, int64_t a_elems, co
                                  int64_t total_ids, const int32_t* blocks, int64_t num_blocks, int has_ignore,
                                  int ignore, int64_t max_bins, int path, int64_t* out, int64_t out_len, int64_t* bad,
                                  void* stream);
+/* Label histograms of a ragged batch (which classes an image holds, and their areas): the same kernel without
+ * the plane b.  images as above with cols = 1, id_count = -1 and b_off unused: the table of image i is its rows
+ * counters at out + out_off, row v counting the pixels of value v in [0, rows - 1), row rows - 1 those equal to
+ * `ignore` (when has_ignore); any other value adds 1 to bad[i].  blocks, max_bins, path, the exact 64-bit counters
+ * and the argument checks are those of m2f_label_pair_counts_ragged. */
+int m2f_label_histogram_ragged(const void* a, int a_bytes, int64_t a_elems, const int64_t* images, int num_images,
+                               const int32_t* blocks, int64_t num_blocks, int has_ignore, int ignore,
+                               int64_t max_bins, int path, int64_t* out, int64_t out_len, int64_t* bad,
+                               void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * COCO polygons -> bit planes (bm2f_amd/polygon.py; the definition, a restatement of rleFrPoly of
