@@ -133,6 +133,8 @@ _SIGNATURES = {
     "m2f_poly_decode_bits_ragged": [_p, _l, _p, _l, _p, _i, _p, _p, _p, _l, _p, _l, _p],
     "m2f_bits_boundary_tiles": [_p, _p, _p],
     "m2f_bits_boundary_ragged": [_p, _l, _i, _p, _p, _p, _p, _l, _i, _p, _p],
+    "m2f_image_views": [_p, _l, _p, _p, _i, _p, _l, _i, _f, _f, _f, _f, _f, _f, _f, _i, _p, _i, _i, _p],
+    "m2f_label_views": [_p, _i, _l, _p, _p, _i, _i, _p, _l, _p, _i, _i, _p],
 }
 
 

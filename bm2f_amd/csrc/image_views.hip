@@ -1,0 +1,440 @@
+// The input pipeline of the reference on the device: the mappers' PIL resize (ResizeTransform ->
+// Image.resize(BILINEAR) for images, NEAREST for label maps and masks), their crop, flip and pad, and the model's
+// (x - pixel_mean) / pixel_std and ImageList.from_tensors, for all V views of a call in one launch.
+//
+// m2f_image_views.  Pillow's 8-bit resize (Resample.c) is integer arithmetic and is restated exactly: per axis a
+// table of (xmin, n) bounds and ksize int32 coefficients at PRECISION_BITS = 22 (built on the host,
+// bm2f_amd/image_views.py), each pass  out = clip8((2^21 + sum_k pixel[xmin + k] * coeff[k]) >> 22),  horizontal
+// first, the intermediate rounded to uint8, an axis whose size does not change skipped.  A view's row of the table
+// (include/bm2f.h) adds a crop window in resized coordinates, a canvas, a mirror of the source (flip_in) or of the
+// crop (flip_out) and a fill byte.  An output element is, in this order,
+//   outside the canvas           pad_value, stored as is
+//   inside crop and image        the PIL pixel p          } as p itself (uint8), float(p), or (float(p) - mean[c]) /
+//   elsewhere in the canvas      the fill byte as p       } std[c]: an fp32 subtract and a correctly rounded fp32
+//                                                           divide (no reciprocal), rounded once more for 16 bits
+//
+// Tile.  A workgroup of 256 threads owns kTW = 64 columns x th rows of one view's (Hp, Wp) output, all 3 channels.
+// 64 columns make a channel's row segment 256 B of fp32 (64 B of uint8), one full-width store per wave, and keep the
+// horizontal halo (ksize - 1 source columns per tile) small against the tile.  th is 16 where it fits and halves
+// (8, 4, 2, 1) until the tallest intermediate of the call fits the budget below; one th serves every view of a
+// launch, so a strongly reduced view makes the others' tiles shorter too.  Per tile:
+//   1. the tile's bounds are read and clamped into LDS (a wrong table can then only give wrong pixels);
+//   2. the source rows the vertical taps of the tile span are staged, kStage bytes at a time, as the contiguous HWC
+//      byte runs the horizontal taps span;
+//   3. the horizontal pass writes the uint8 intermediate [3][rows][64] (planar, so the vertical pass reads
+//      neighbouring bytes in neighbouring lanes) -- it exists only in LDS;
+//   4. the vertical pass, the crop / flip addressing, HWC -> CHW and the normalisation are the epilogue; every
+//      element of the tile is stored once, pads included.  No atomics.
+//
+// LDS budget (bytes): intermediate kInter = 49152 (256 rows), stage kStage = 24576, bounds (16 + 64) * 12 = 960:
+// 74688, so that two workgroups share a CU's 163840 B.  The kernel is a chain of dependent LDS reads and integer
+// multiply-adds with no MFMA; two workgroups (8 waves per CU) are what the LDS leaves, and registers do not bind
+// before that.  Speed was not a design input beyond this; tools/input_pipeline_bench.py records what it reaches.
+//
+// Limits: ksize <= M2F_VIEW_MAX_KSIZE = 131 per axis, i.e. any up-scale and a down-scale of at most 65x.  At th = 1
+// the intermediate holds ksize + 1 <= 132 rows and a staged row spans at most 63 * 65 + 132 columns = 12681 B, so
+// every admitted view fits; anything beyond is refused with M2F_EUNSUPPORTED before a launch.
+//
+// m2f_label_views is the nearest-neighbour gather (ImagingScaleAffine's index tables, built on the host) with the
+// same crop, flips, canvas and pad on (P, H, W) planes of 1, 2 or 4 byte elements: one thread per output element.
+//
+// Both entry points take the table twice: views_host is checked row by row against the source, table and output
+// ranges before anything is launched (M2F_EUNSUPPORTED names the row), views_dev is what the kernels read, and
+// they repeat the same check on it, so a device copy that differs from the checked one is skipped, not trusted.
+#include "bm2f.h"
+#include "common.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+namespace {
+
+constexpr int kF = M2F_VIEW_FIELDS;
+constexpr int kTW = 64, kTHMax = 16;
+constexpr int kInter = 49152, kStage = 24576;
+constexpr int kInterRows = kInter / (3 * kTW);  // 256
+constexpr int kMaxK = M2F_VIEW_MAX_KSIZE;
+constexpr int64_t kI31 = 0x7fffffff, kMaxNumel = int64_t{1} << 48;
+
+struct Row {
+  int64_t off, stride, pstride, tx, ty;
+  int H, W, rh, rw, cy0, cx0, ch, cw, Hc, Wc, kx, ky, fill;
+  bool flip_in, flip_out;
+};
+
+struct Bound {  // one output row / column of a tile: first tap relative to the window, taps, coefficient offset
+  int start, n, coef;
+};
+
+__host__ __device__ inline bool in31(int64_t v) { return v >= -kI31 && v <= kI31; }
+// a * b <= limit for non-negative values, without forming a product that could overflow
+__host__ __device__ inline bool mul_le(int64_t a, int64_t b, int64_t limit) { return a == 0 || b <= limit / a; }
+
+// One table row, checked against everything passed by value.  A source pixel is 3 elements of an image (HWC bytes) and
+// 1 of a label plane; planes is 1 for an image.  image: the bilinear tables (2 * out bounds + out * ksize coefficients per
+// resized axis, none for a skipped one); else the nearest tables (out indices per axis).
+__host__ __device__ inline bool load_row(const int64_t* r, bool image, int planes, int64_t src_numel,
+                                         int64_t tables_numel, int out_h, int out_w, Row* o) {
+  for (int i = 1; i < kF; ++i)
+    if (!in31(r[i]) && i != 3 && i != 14 && i != 15 && i != 17) return false;
+  const int64_t off = r[0], H = r[1], W = r[2], stride = r[3], rh = r[4], rw = r[5], ch = r[8], cw = r[9], Hc = r[10],
+                Wc = r[11], tx = r[14], ty = r[15], fill = r[16], ps = r[17], kx = r[18], ky = r[19];
+  const int64_t e = image ? 3 : 1;
+  if (H <= 0 || W <= 0 || rh <= 0 || rw <= 0 || ch <= 0 || cw <= 0 || Hc <= 0 || Wc <= 0) return false;
+  if (Hc > out_h || Wc > out_w) return false;
+  if (src_numel > kMaxNumel || off < 0 || off > src_numel || stride < W * e || ps < 0) return false;
+  // the last element read is off + (planes - 1) ps + (H - 1) stride + W e - 1: three terms of at most 2^48 each
+  const int64_t room = src_numel - off;
+  if (!mul_le(planes - 1, ps, room) || !mul_le(H - 1, stride, room)) return false;
+  if ((planes - 1) * ps + (H - 1) * stride + W * e > room) return false;
+  if (tx < 0 || ty < 0 || tx > tables_numel || ty > tables_numel) return false;
+  if (image) {
+    if (fill < 0 || fill > 255) return false;
+    if (kx < 0 || ky < 0 || kx > kMaxK || ky > kMaxK) return false;
+    if ((kx == 0) != (rw == W) || (ky == 0) != (rh == H)) return false;
+    // an axis's table is 2 * out bounds, then out * ksize coefficients, indexed with 32 bits
+    if (rw * (2 + kx) > kI31 || rh * (2 + ky) > kI31) return false;
+    if (kx && rw * (2 + kx) > tables_numel - tx) return false;
+    if (ky && rh * (2 + ky) > tables_numel - ty) return false;
+  } else {
+    if (rw > tables_numel - tx || rh > tables_numel - ty) return false;
+  }
+  o->off = off; o->stride = stride; o->pstride = ps; o->tx = tx; o->ty = ty;
+  o->H = static_cast<int>(H); o->W = static_cast<int>(W); o->rh = static_cast<int>(rh); o->rw = static_cast<int>(rw);
+  o->cy0 = static_cast<int>(r[6]); o->cx0 = static_cast<int>(r[7]); o->ch = static_cast<int>(ch);
+  o->cw = static_cast<int>(cw); o->Hc = static_cast<int>(Hc); o->Wc = static_cast<int>(Wc);
+  o->kx = static_cast<int>(kx); o->ky = static_cast<int>(ky); o->fill = static_cast<int>(fill);
+  o->flip_in = r[12] != 0; o->flip_out = r[13] != 0;
+  return true;
+}
+
+// the resized column of canvas column x (a 64-bit value: cx0 is any int32), valid when x < cw and it is in [0, rw)
+__host__ __device__ inline int64_t resized_col(const Row& g, int x) {
+  return static_cast<int64_t>(g.cx0) + (g.flip_out ? g.cw - 1 - x : x);
+}
+
+template <typename T>
+struct Store {
+  static __device__ __forceinline__ T pixel(int p, bool norm, float mean, float sd) {
+    const float f = static_cast<float>(p);
+    return static_cast<T>(norm ? __fdiv_rn(__fsub_rn(f, mean), sd) : f);
+  }
+  static __device__ __forceinline__ T pad(float v) { return static_cast<T>(v); }
+};
+template <>
+struct Store<uint8_t> {
+  static __device__ __forceinline__ uint8_t pixel(int p, bool, float, float) { return static_cast<uint8_t>(p); }
+  static __device__ __forceinline__ uint8_t pad(float v) {
+    return static_cast<uint8_t>(min(max(static_cast<int>(v), 0), 255));
+  }
+};
+
+__device__ __forceinline__ int clip8(int acc) { return min(max(acc >> 22, 0), 255); }
+
+struct Norm {  // read with constant indices only: a kernel argument indexed at run time would move to scratch
+  float m0, m1, m2, s0, s1, s2;
+  int on;
+};
+
+// grid (ceil(Wp / 64), ceil(Hp / th), V), 256 threads, dynamic LDS kInter + kStage + bounds
+template <typename T>
+__global__ void __launch_bounds__(256) image_views_kernel(const uint8_t* __restrict__ src, int64_t src_numel,
+                                                          const int64_t* __restrict__ views,
+                                                          const int32_t* __restrict__ tables, int64_t tables_numel,
+                                                          Norm nm, float pad_value, T* __restrict__ out, int Hp,
+                                                          int Wp, int th) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  uint8_t* inter = smem;              // [3][kInterRows][kTW]
+  uint8_t* stage = smem + kInter;     // [rows of a chunk][span * 3]
+  Bound* ys = reinterpret_cast<Bound*>(smem + kInter + kStage);  // [kTHMax]
+  Bound* xs = ys + kTHMax;                                       // [kTW]
+  __shared__ int s_win[4];            // window: first source row, rows, first table column, columns
+
+  const int tid = threadIdx.x, v = blockIdx.z;
+  const int y0 = blockIdx.y * th, x0 = blockIdx.x * kTW;
+  Row g;
+  if (!load_row(views + static_cast<int64_t>(v) * kF, true, 1, src_numel, tables_numel, Hp, Wp, &g)) return;
+
+  // the tile's rows and columns that show the resized image: both ranges are contiguous
+  const int ye = min(min(y0 + th, g.ch), g.Hc), xe = min(min(x0 + kTW, g.cw), g.Wc);
+  int64_t rya = 0, ryb = -1, rxa = 0, rxb = -1;
+  if (ye > y0 && xe > x0) {
+    rya = max(static_cast<int64_t>(g.cy0) + y0, int64_t{0});
+    ryb = min(static_cast<int64_t>(g.cy0) + ye - 1, static_cast<int64_t>(g.rh) - 1);
+    const int64_t a = resized_col(g, x0), b = resized_col(g, xe - 1);
+    rxa = max(min(a, b), int64_t{0});
+    rxb = min(max(a, b), static_cast<int64_t>(g.rw) - 1);
+  }
+  const int ny = static_cast<int>(max(ryb - rya + 1, int64_t{0})), nx = static_cast<int>(max(rxb - rxa + 1, int64_t{0}));
+  const bool any = ny > 0 && nx > 0;  // uniform
+  const int32_t* tY = tables + g.ty;
+  const int32_t* tX = tables + g.tx;
+
+  if (any) {
+    // bounds of the tile's resized rows (wave 0) and columns (wave 1), clamped to the source
+    if (tid < kTHMax) {
+      Bound b{0, 0, 0};
+      if (tid < ny) {
+        const int ry = static_cast<int>(rya) + tid;
+        if (g.ky) {
+          b.start = min(max(tY[2 * ry], 0), g.H);
+          b.n = min(min(max(tY[2 * ry + 1], 0), g.ky), g.H - b.start);
+          b.coef = 2 * g.rh + ry * g.ky;
+        } else {
+          b.start = ry;
+          b.n = 1;
+        }
+      }
+      ys[tid] = b;
+    } else if (tid >= 64 && tid < 64 + kTW) {
+      const int j = tid - 64;
+      Bound b{0, 0, 0};
+      if (j < nx) {
+        const int rx = static_cast<int>(rxa) + j;
+        if (g.kx) {
+          b.start = min(max(tX[2 * rx], 0), g.W);
+          b.n = min(min(max(tX[2 * rx + 1], 0), g.kx), g.W - b.start);
+          b.coef = 2 * g.rw + rx * g.kx;
+        } else {
+          b.start = rx;
+          b.n = 1;
+        }
+      }
+      xs[j] = b;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int lo = 0x7fffffff, hi = 0;
+      for (int i = 0; i < ny; ++i) {
+        lo = min(lo, ys[i].start);
+        hi = max(hi, ys[i].start + ys[i].n);
+      }
+      s_win[0] = min(lo, hi);
+      s_win[1] = min(max(hi - lo, 0), kInterRows);
+    } else if (tid == 64) {
+      int lo = 0x7fffffff, hi = 0;
+      for (int i = 0; i < nx; ++i) {
+        lo = min(lo, xs[i].start);
+        hi = max(hi, xs[i].start + xs[i].n);
+      }
+      s_win[2] = min(lo, hi);
+      s_win[3] = min(max(hi - lo, 0), kStage / 3);
+    }
+    __syncthreads();
+    const int wy = s_win[0], R = s_win[1], wx = s_win[2], span = s_win[3];
+    // taps relative to the window; a tap past it (only a wrong table has one) is dropped
+    if (tid < ny) {
+      Bound b = ys[tid];
+      b.start -= wy;
+      b.n = max(min(b.n, R - b.start), 0);
+      ys[tid] = b;
+    } else if (tid >= 64 && tid < 64 + nx) {
+      Bound b = xs[tid - 64];
+      b.start -= wx;
+      b.n = max(min(b.n, span - b.start), 0);
+      xs[tid - 64] = b;
+    }
+    const int rowbytes = span * 3;
+    // table columns [wx, wx + span) are source columns [W - wx - span, W - wx) of a mirrored source
+    const int scol0 = g.flip_in ? g.W - wx - span : wx;
+    const int RC = rowbytes > 0 ? min(kStage / rowbytes, R) : 0;
+    __syncthreads();
+    for (int r0 = 0; r0 < R && RC > 0; r0 += RC) {
+      const int rows = min(RC, R - r0);
+      const uint8_t* sp = src + g.off + static_cast<int64_t>(wy + r0) * g.stride + static_cast<int64_t>(scol0) * 3;
+      for (int idx = tid; idx < rows * rowbytes; idx += 256) {
+        const int rr = idx / rowbytes, b = idx - rr * rowbytes;
+        stage[idx] = sp[static_cast<int64_t>(rr) * g.stride + b];
+      }
+      __syncthreads();
+      for (int idx = tid; idx < rows * 3 * nx; idx += 256) {
+        const int col = idx % nx, q = idx / nx, c = q % 3, rr = q / 3;
+        const Bound b = xs[col];
+        const uint8_t* sr = stage + rr * rowbytes + c;
+        int p;
+        if (g.kx) {
+          int acc = 1 << 21;
+          const int32_t* kk = tX + b.coef;
+          for (int k = 0; k < b.n; ++k) {
+            const int i = b.start + k;
+            acc += static_cast<int>(sr[(g.flip_in ? span - 1 - i : i) * 3]) * kk[k];
+          }
+          p = clip8(acc);
+        } else {
+          p = b.n ? sr[(g.flip_in ? span - 1 - b.start : b.start) * 3] : 0;
+        }
+        inter[(c * kInterRows + r0 + rr) * kTW + col] = static_cast<uint8_t>(p);
+      }
+      __syncthreads();
+    }
+  }
+
+  const int64_t plane = static_cast<int64_t>(Hp) * Wp;
+  T* ov = out + static_cast<int64_t>(v) * 3 * plane;
+  for (int idx = tid; idx < 3 * th * kTW; idx += 256) {
+    const int x = idx % kTW, q = idx / kTW, y = q % th, c = q / th;
+    const int gy = y0 + y, gx = x0 + x;
+    if (gy >= Hp || gx >= Wp) continue;
+    T val;
+    if (gy >= g.Hc || gx >= g.Wc) {
+      val = Store<T>::pad(pad_value);
+    } else {
+      int p = g.fill;
+      const int64_t ry = static_cast<int64_t>(g.cy0) + gy, rx = resized_col(g, gx);
+      if (any && gy < g.ch && gx < g.cw && ry >= rya && ry <= ryb && rx >= rxa && rx <= rxb) {
+        const Bound b = ys[static_cast<int>(ry - rya)];
+        const uint8_t* ic = inter + (c * kInterRows + b.start) * kTW + static_cast<int>(rx - rxa);
+        if (g.ky) {
+          int acc = 1 << 21;
+          const int32_t* kk = tY + b.coef;
+          for (int k = 0; k < b.n; ++k) acc += static_cast<int>(ic[k * kTW]) * kk[k];
+          p = clip8(acc);
+        } else {
+          p = b.n ? ic[0] : 0;
+        }
+      }
+      val = Store<T>::pixel(p, nm.on != 0, c == 0 ? nm.m0 : c == 1 ? nm.m1 : nm.m2,
+                            c == 0 ? nm.s0 : c == 1 ? nm.s1 : nm.s2);
+    }
+    ov[c * plane + static_cast<int64_t>(gy) * Wp + gx] = val;
+  }
+}
+
+// one thread per output element, grid-stride; out (V, P, Hp, Wp)
+template <typename T>
+__global__ void __launch_bounds__(256) label_views_kernel(const T* __restrict__ src, int64_t src_numel,
+                                                          const int64_t* __restrict__ views, int V, int P,
+                                                          const int32_t* __restrict__ tables, int64_t tables_numel,
+                                                          T* __restrict__ out, int Hp, int Wp) {
+  const int64_t plane = static_cast<int64_t>(Hp) * Wp, per_view = plane * P, total = per_view * V;
+  Row g;
+  int cur = -1;
+  bool ok = false;
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += 256ll * gridDim.x) {
+    const int v = static_cast<int>(i / per_view);
+    const int64_t rem = i - v * per_view;
+    const int p = static_cast<int>(rem / plane);
+    const int64_t pix = rem - p * plane;
+    const int gy = static_cast<int>(pix / Wp), gx = static_cast<int>(pix - static_cast<int64_t>(gy) * Wp);
+    if (v != cur) {  // a thread's elements change their view rarely
+      cur = v;
+      ok = load_row(views + static_cast<int64_t>(v) * kF, false, P, src_numel, tables_numel, Hp, Wp, &g);
+    }
+    if (!ok) continue;
+    T val = static_cast<T>(g.fill);  // the canvas fill is the batch pad as well
+    const int64_t ry = static_cast<int64_t>(g.cy0) + gy, rx = resized_col(g, gx);
+    if (gy < g.ch && gx < g.cw && gy < g.Hc && gx < g.Wc && ry >= 0 && ry < g.rh && rx >= 0 && rx < g.rw) {
+      const int sy = min(max(tables[g.ty + ry], 0), g.H - 1);
+      int sx = min(max(tables[g.tx + rx], 0), g.W - 1);
+      if (g.flip_in) sx = g.W - 1 - sx;
+      val = src[g.off + p * g.pstride + sy * g.stride + sx];
+    }
+    out[i] = val;
+  }
+}
+
+// rows of the intermediate / columns of the stage that `tile` outputs of an axis reduced by in / out can span
+int span_bound(int tile, int64_t in, int64_t out, int ksize) {
+  if (ksize == 0) return tile;
+  const double scale = static_cast<double>(in) / static_cast<double>(out);
+  return static_cast<int>(std::ceil((tile - 1) * scale)) + ksize + 1;
+}
+
+int check_common(const char* fn, const void* src, int64_t src_numel, const int64_t* vh, const int64_t* vd, int V,
+                 const int32_t* tables, int64_t tables_numel, const void* out, int out_h, int out_w) {
+  if (!src || !vh || !vd || !tables || !out) return m2f::fail(M2F_EINVAL, "%s: null pointer", fn);
+  if (V <= 0 || src_numel <= 0 || tables_numel <= 0 || out_h <= 0 || out_w <= 0)
+    return m2f::fail(M2F_EINVAL, "%s: sizes must be positive", fn);
+  if (src_numel > kMaxNumel || V > 65535 || out_h > 65535 || static_cast<int64_t>(out_h) * out_w > kI31)
+    return m2f::fail(M2F_EUNSUPPORTED, "%s: sizes exceed the grid / index range", fn);
+  return M2F_OK;
+}
+
+}  // namespace
+
+extern "C" int m2f_image_views(const void* src, int64_t src_numel, const int64_t* views_host, const int64_t* views_dev,
+                               int num_views, const int32_t* tables, int64_t tables_numel, int normalize, float mean0,
+                               float mean1, float mean2, float std0, float std1, float std2, float pad_value,
+                               int out_dtype, void* out, int out_h, int out_w, void* stream) {
+  const char* fn = "m2f_image_views";
+  if (int rc = check_common(fn, src, src_numel, views_host, views_dev, num_views, tables, tables_numel, out, out_h,
+                            out_w))
+    return rc;
+  if (!m2f::is_float_dtype(out_dtype) && out_dtype != M2F_U8)
+    return m2f::fail(M2F_EUNSUPPORTED, "%s: dtype %d", fn, out_dtype);
+  if (normalize && out_dtype == M2F_U8)
+    return m2f::fail(M2F_EUNSUPPORTED, "%s: a uint8 output takes no mean / std", fn);
+  if (normalize && !(std0 != 0.f && std1 != 0.f && std2 != 0.f))
+    return m2f::fail(M2F_EINVAL, "%s: std must be nonzero", fn);
+  int th = kTHMax;
+  for (int v = 0; v < num_views; ++v) {
+    const int64_t* r = views_host + static_cast<int64_t>(v) * kF;
+    Row g;
+    if (r[18] > kMaxK || r[19] > kMaxK)
+      return m2f::fail(M2F_EUNSUPPORTED, "%s: view %d: ksize (%lld, %lld) > %d, a down-scale beyond 65x", fn, v,
+                       static_cast<long long>(r[19]), static_cast<long long>(r[18]), kMaxK);
+    if (!load_row(r, true, 1, src_numel, tables_numel, out_h, out_w, &g))
+      return m2f::fail(M2F_EUNSUPPORTED, "%s: view %d: a size is not positive, or the source, tables or canvas leave "
+                       "their ranges", fn, v);
+    // a resampled axis's ksize is the one its sizes imply, so that the bounds below hold for a correct table
+    const int want_x = g.kx ? 2 * static_cast<int>(std::ceil(std::fmax(static_cast<double>(g.W) / g.rw, 1.0))) + 1 : 0;
+    const int want_y = g.ky ? 2 * static_cast<int>(std::ceil(std::fmax(static_cast<double>(g.H) / g.rh, 1.0))) + 1 : 0;
+    if (g.kx != want_x || g.ky != want_y)
+      return m2f::fail(M2F_EUNSUPPORTED, "%s: view %d: ksize (%d, %d) does not belong to its sizes", fn, v, g.ky, g.kx);
+    if (span_bound(kTW, g.W, g.rw, g.kx) * 3 > kStage)
+      return m2f::fail(M2F_EUNSUPPORTED, "%s: view %d: a tile's source columns exceed the stage", fn, v);
+    while (th > 1 && span_bound(th, g.H, g.rh, g.ky) > kInterRows) th >>= 1;
+    if (span_bound(th, g.H, g.rh, g.ky) > kInterRows)
+      return m2f::fail(M2F_EUNSUPPORTED, "%s: view %d: a tile's source rows exceed the intermediate", fn, v);
+  }
+  const Norm nm{mean0, mean1, mean2, std0, std1, std2, normalize != 0};
+  const int lds = kInter + kStage + (kTHMax + kTW) * static_cast<int>(sizeof(Bound));
+  const dim3 grid(m2f::ceil_div(out_w, kTW), m2f::ceil_div(out_h, th), num_views);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc = M2F_OK;
+  auto launch = [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    rc = m2f::set_max_lds(reinterpret_cast<const void*>(&image_views_kernel<T>), lds, fn);
+    if (rc) return;
+    image_views_kernel<T><<<grid, 256, lds, st>>>(static_cast<const uint8_t*>(src), src_numel, views_dev, tables,
+                                                  tables_numel, nm, pad_value, static_cast<T*>(out), out_h, out_w, th);
+    rc = m2f::check_launch(fn);
+  };
+  if (out_dtype == M2F_U8) launch(m2f::Tag<uint8_t>{});
+  else m2f::dispatch_float(out_dtype, launch);
+  return rc;
+}
+
+extern "C" int m2f_label_views(const void* src, int elem_bytes, int64_t src_numel, const int64_t* views_host,
+                               const int64_t* views_dev, int num_views, int num_planes, const int32_t* tables,
+                               int64_t tables_numel, void* out, int out_h, int out_w, void* stream) {
+  const char* fn = "m2f_label_views";
+  if (int rc = check_common(fn, src, src_numel, views_host, views_dev, num_views, tables, tables_numel, out, out_h,
+                            out_w))
+    return rc;
+  if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4)
+    return m2f::fail(M2F_EUNSUPPORTED, "%s: element size %d", fn, elem_bytes);
+  if (num_planes <= 0) return m2f::fail(M2F_EINVAL, "%s: sizes must be positive", fn);
+  if (!m2f::aligned(src, elem_bytes) || !m2f::aligned(out, elem_bytes))
+    return m2f::fail(M2F_EINVAL, "%s: misaligned pointer", fn);
+  for (int v = 0; v < num_views; ++v) {
+    Row g;
+    if (!load_row(views_host + static_cast<int64_t>(v) * kF, false, num_planes, src_numel, tables_numel, out_h, out_w,
+                  &g))
+      return m2f::fail(M2F_EUNSUPPORTED, "%s: view %d: a size is not positive, or the source, tables or canvas leave "
+                       "their ranges", fn, v);
+  }
+  const int64_t total = static_cast<int64_t>(num_views) * num_planes * out_h * out_w;
+  const unsigned grid = static_cast<unsigned>(std::min<int64_t>((total + 255) / 256, 8192));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  auto launch = [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    label_views_kernel<T><<<grid, 256, 0, st>>>(static_cast<const T*>(src), src_numel, views_dev, num_views, num_planes,
+                                                tables, tables_numel, static_cast<T*>(out), out_h, out_w);
+  };
+  if (elem_bytes == 1) launch(m2f::Tag<uint8_t>{});
+  else if (elem_bytes == 2) launch(m2f::Tag<int16_t>{});
+  else launch(m2f::Tag<int32_t>{});
+  return m2f::check_launch(fn);
+}

@@ -948,6 +948,51 @@ int m2f_bits_boundary_ragged(const int32_t* words, int64_t total_words, int num_
                              const int64_t* offsets, const int32_t* dilations, const int32_t* blocks,
                              int64_t num_blocks, int max_dilation, int32_t* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Input views (bm2f_amd/image_views.py; the definition, a restatement of Pillow's 8-bit resize, is in DESIGN.md
+ * §3): resize, crop, flip, canvas fill, normalise, pad and stack of the V views of a call in one launch.
+ *
+ *   views (V, M2F_VIEW_FIELDS) int64, one row per view =
+ *       0 src_off   element offset of the view's source in `src`      1 H, 2 W   source size
+ *       3 stride    elements between source rows (>= 3 W for an image, >= W for a plane: a crop view of a larger
+ *                   tensor is read in place)
+ *       4 rh, 5 rw  the resized size                 6 cy0, 7 cx0, 8 ch, 9 cw   crop window in resized coordinates
+ *       10 Hc, 11 Wc  the canvas (<= out_h, out_w)   12 flip_in   mirror the source columns before the resize
+ *       13 flip_out   mirror the crop window's columns after the resize
+ *       14 tab_x, 15 tab_y   element offsets of the two axes' tables in `tables`
+ *       16 fill     the value of a canvas element outside crop and resized image
+ *       17 plane_stride   elements between the planes of a label source (images: unused)
+ *       18 kx, 19 ky      ksize per axis of an image, 0 for an axis whose size does not change (labels: unused)
+ *     Output element (y, x) of view v:  y >= Hc or x >= Wc: the pad.  Else with ry = cy0 + y and rx = cx0 + (flip_out ?
+ *     cw - 1 - x : x): the resized pixel (ry, rx) when y < ch, x < cw, 0 <= ry < rh and 0 <= rx < rw, else fill.
+ *   tables  int32.  Image axis (in -> out, ksize k > 0): 2 * out values (xmin, n) then out * k coefficients at 22
+ *           fractional bits, a pass being clip8((2^21 + sum_{j < n} pixel[xmin + j] * coeff[j]) >> 22); horizontal
+ *           first, its result rounded to uint8.  k must be 2 * ceil(max(in / out, 1)) + 1 <= M2F_VIEW_MAX_KSIZE.
+ *           Label axis: out source indices.  The kernels clamp what they read from `tables` into the source.
+ *   views_host / views_dev   the same table in host and in device memory: the host copy is checked row by row
+ *           before anything is launched, the kernels read the device copy and skip a row that fails the same check.
+ *
+ *   m2f_image_views   src uint8 HWC with 3 channels; out (V, 3, out_h, out_w) of out_dtype (M2F_F32 / F16 / BF16 /
+ *                     M2F_U8).  A pixel p is stored as p (uint8), float(p), or with `normalize`
+ *                     (float(p) - mean[c]) / std[c] in fp32 with a correctly rounded division, rounded once more for
+ *                     a 16-bit output; fill is stored the same way, pad_value as it is.
+ *   m2f_label_views   src (num_planes, H, W) planes of elem_bytes 1, 2 or 4 per view, out (V, num_planes, out_h,
+ *                     out_w) of the same element type; nearest gather; the pad is the view's fill.
+ * Every output element is stored exactly once; no atomics.  Null pointers, non-positive counts or misaligned
+ * pointers give M2F_EINVAL.  An unknown dtype, mean / std with a uint8 output, a ksize beyond
+ * M2F_VIEW_MAX_KSIZE (a down-scale beyond 65x) and a row whose sizes are not positive or whose source, tables
+ * or canvas leave src_numel, tables_numel or (out_h, out_w) give M2F_EUNSUPPORTED.  All before any HIP call.
+ * ------------------------------------------------------------------------------------------- */
+enum { M2F_U8 = 3 };
+enum { M2F_VIEW_FIELDS = 20, M2F_VIEW_MAX_KSIZE = 131 };
+int m2f_image_views(const void* src, int64_t src_numel, const int64_t* views_host, const int64_t* views_dev,
+                    int num_views, const int32_t* tables, int64_t tables_numel, int normalize, float mean0,
+                    float mean1, float mean2, float std0, float std1, float std2, float pad_value, int out_dtype,
+                    void* out, int out_h, int out_w, void* stream);
+int m2f_label_views(const void* src, int elem_bytes, int64_t src_numel, const int64_t* views_host,
+                    const int64_t* views_dev, int num_views, int num_planes, const int32_t* tables,
+                    int64_t tables_numel, void* out, int out_h, int out_w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
