@@ -21,6 +21,9 @@ from .panoptic_eval import (COCOPanopticEvaluator, PanopticGroundTruth, PQStat, 
 from .tta import SemanticSegmentorWithTTA, semantic_inference_tta, tta_view_sizes  # noqa: F401
 from .image_views import (DeviceTTAMapper, View, image_views, label_views, lsj_view,  # noqa: F401
                           preprocess_test_images, resize_image, resize_shortest_edge_size)
+from .color_aug import ColorAug, draw_color_aug_ssd, draw_video_photometric  # noqa: F401
+from .train_mappers import (PanopticTrainMapper, SemanticTrainMapper, semantic_train_view,  # noqa: F401
+                            video_clip_views)
 from .sem_seg_eval import SemSegEvaluator, evaluate_sem_seg, sem_seg_metrics  # noqa: F401
 from .polygon import (ann_to_rle, convert_polygons_to_rle, polygon_crossings, polygons_to_bits,  # noqa: F401
                       polygons_to_bits_ragged, polygons_to_rle)

@@ -135,6 +135,10 @@ _SIGNATURES = {
     "m2f_bits_boundary_ragged": [_p, _l, _i, _p, _p, _p, _p, _l, _i, _p, _p],
     "m2f_image_views": [_p, _l, _p, _p, _i, _p, _l, _i, _f, _f, _f, _f, _f, _f, _f, _i, _p, _i, _i, _p],
     "m2f_label_views": [_p, _i, _l, _p, _p, _i, _i, _p, _l, _p, _i, _i, _p],
+    "m2f_image_views_color": [_p, _l, _p, _p, _i, _p, _l, _p, _p, _l, _p, _i, _f, _f, _f, _f, _f, _f, _f, _i, _p, _i,
+                              _i, _p],
+    "m2f_image_views_sum_workspace": [_p, _i, _i, _i, _p],
+    "m2f_image_views_sum": [_p, _l, _p, _p, _i, _p, _l, _p, _p, _l, _i, _i, _p, _l, _p],
 }
 
 

@@ -16,8 +16,15 @@ tests/golden/image_views.npz records Pillow's outputs for machines without it). 
 (:func:`resize_shortest_edge_size`, :func:`lsj_view`) restate detectron2's ``ResizeShortestEdge``, ``ResizeScale``
 and ``FixedSizeCrop``; detectron2 is not installed where this was written and they have not been run against it.
 
-Out of scope: reading files, ``ColorAugSSDTransform`` (OpenCV's HSV), brightness / contrast / saturation blends,
-rotation, the retry loop of ``RandomCrop_CategoryAreaConstraint`` (pass the chosen window as ``View.crop``),
+Colour: a :class:`View` may carry a :class:`bm2f_amd.color_aug.ColorAug` (``ColorAugSSDTransform`` or the video
+mappers' brightness / contrast / saturation blends, defined in :mod:`bm2f_amd.color_aug`).  The operations run inside
+the same kernel (``m2f_image_views_color``) on the pixels that show the image, never on fill or pad; a contrast blend
+costs one more launch before it (``m2f_image_views_sum``, the view's exact integer sum; the host never reads it).
+With every ``color`` left None the call is ``m2f_image_views`` exactly as before.  The colour definitions have not
+been run against cv2 or detectron2.
+
+Out of scope: reading files, rotation (``cv2.warpAffine``), source-space ``T.RandomCrop`` of the video mappers,
+polygon annotations, the retry loop of ``RandomCrop_CategoryAreaConstraint`` (pass the chosen window as ``View.crop``),
 polygon-space transforms (rasterise with :mod:`bm2f_amd.polygon` at the output size instead) and the resize of
 float images (detectron2 uses ``F.interpolate`` there, not PIL).
 """
@@ -33,6 +40,7 @@ import numpy as np
 import torch
 
 from . import _native
+from . import color_aug as _ca
 from .tta import tta_view_sizes
 
 _FIELDS = 20          # include/bm2f.h: M2F_VIEW_FIELDS
@@ -52,6 +60,8 @@ class View:
     flip_in mirrors the source before the resize (the COCO LSJ order: RandomFlip, ResizeScale, FixedSizeCrop);
     flip_out mirrors the crop window after it (the TTA, semantic and video order: resize, crop, flip).  fill: the
     byte of canvas pixels outside crop and image (128 for LSJ images); label_views uses its ``seg_pad`` instead.
+    color: a :class:`bm2f_amd.color_aug.ColorAug` applied to the pixels that show the image, after resize, crop and
+    flip (the mappers' order) and before the normalisation; label_views ignores it.
     """
     size: tuple
     source: int = 0
@@ -60,6 +70,7 @@ class View:
     flip_in: bool = False
     flip_out: bool = False
     fill: int = 0
+    color: _ca.ColorAug | None = None
 
 
 # ------------------------------------------------------------------------------------------------ host tables
@@ -204,6 +215,13 @@ class _Plan:
                        kx, ky)
             self.sizes.append(canvas)
         self.rows = rows
+        # the colour table and OpenCV's two division tables, only when a view asks for them
+        self.colors, self.hsv_off = None, -1
+        colored = [getattr(v, "color", None) for v in self.views] if image else []
+        if any(c is not None and c.ops for c in colored):
+            self.colors = np.stack([_ca.encode(c) for c in colored])
+            if any(c is not None and c.needs_hsv for c in colored):
+                self.hsv_off = put(("hsv",), _ca.hsv_tables())
         self.tables = np.concatenate(parts) if parts else np.zeros(1, dtype=np.int32)
 
     def padded(self, size_divisibility):
@@ -222,13 +240,18 @@ def _span(tensors, extents):
 
 
 def _upload(plan, dev):
-    """The view table and the axis tables in one buffer, one copy: -> (device buffer, rows pointer, tables pointer)."""
+    """The view table, the colour table (when there is one) and the axis tables in one buffer, one copy: -> (device
+    buffer, rows pointer, tables pointer, colours pointer or None)."""
     V = plan.rows.shape[0]
-    buf = np.empty(V * _FIELDS * 2 + plan.tables.size, dtype=np.int32)
+    nc = 0 if getattr(plan, "colors", None) is None else V * _ca.FIELDS * 2
+    buf = np.empty(V * _FIELDS * 2 + nc + plan.tables.size, dtype=np.int32)
     buf[:V * _FIELDS * 2] = plan.rows.reshape(-1).view(np.int32)
-    buf[V * _FIELDS * 2:] = plan.tables
+    if nc:
+        buf[V * _FIELDS * 2:V * _FIELDS * 2 + nc] = np.ascontiguousarray(plan.colors).reshape(-1).view(np.int32)
+    buf[V * _FIELDS * 2 + nc:] = plan.tables
     d = torch.from_numpy(buf).to(dev, non_blocking=True)
-    return d, d.data_ptr(), d.data_ptr() + V * _FIELDS * 8
+    rows = d.data_ptr()
+    return d, rows, rows + V * _FIELDS * 8 + nc * 4, (rows + V * _FIELDS * 8 if nc else None)
 
 
 def _host_ptr(a):
@@ -277,6 +300,13 @@ def _place_np(resized, row, fill, channels_last):
     return canvas
 
 
+def _color_np(canvas, resized_hw, row, aug):
+    """The colour operations on the pixels of a (3, Hc, Wc) canvas that show the image, in place: fill stays."""
+    shown = _place_np(np.ones(tuple(resized_hw) + (1,), dtype=np.uint8), row, 0, True)[0].astype(bool)
+    if shown.any():
+        canvas[:, shown] = _ca.apply_color(np.ascontiguousarray(canvas[:, shown].T)[None], aug)[0].T
+
+
 def _norm_torch(canvas, mean, std, out_dtype):
     """uint8 (3, h, w) tensor -> the stored values: the model's (x - pixel_mean) / pixel_std in fp32."""
     if out_dtype == torch.uint8:
@@ -316,11 +346,25 @@ def _launch_image(src_ptr, src_numel, plan, rows, out, mean, std, pad_value):
     """rows: plan.rows with the source offsets and strides filled in.  One upload, one launch."""
     dev = out.device
     rows = np.ascontiguousarray(rows, dtype=np.int64)
-    keep, rows_dev, tables_dev = _upload(_with_rows(plan, rows), dev)
+    keep, rows_dev, tables_dev, colors_dev = _upload(_with_rows(plan, rows), dev)
     m, s = ((0.0,) * 3, (1.0,) * 3) if mean is None else (mean.tolist(), std.tolist())
-    _native.call("m2f_image_views", src_ptr, src_numel, _host_ptr(rows), rows_dev, rows.shape[0], tables_dev,
-                 plan.tables.size, int(mean is not None), *m, *s, float(pad_value), _out_code(out.dtype),
-                 out.data_ptr(), out.shape[2], out.shape[3], _native.stream(dev))
+    store = (int(mean is not None), *m, *s, float(pad_value), _out_code(out.dtype), out.data_ptr(), out.shape[2],
+             out.shape[3], _native.stream(dev))
+    if colors_dev is None:
+        _native.call("m2f_image_views", src_ptr, src_numel, _host_ptr(rows), rows_dev, rows.shape[0], tables_dev,
+                     plan.tables.size, *store)
+    else:
+        colors = np.ascontiguousarray(plan.colors, dtype=np.float64)
+        common = (src_ptr, src_numel, _host_ptr(rows), rows_dev, rows.shape[0], tables_dev, plan.tables.size,
+                  _host_ptr(colors), colors_dev, int(plan.hsv_off))
+        sums = None
+        if bool((colors[:, 2] >= 0).any()):                  # a contrast blend: the views' sums first, device only
+            sums = _native.workspace("m2f_image_views_sum_workspace", _host_ptr(rows), rows.shape[0], out.shape[2],
+                                     out.shape[3], device=dev, dtype=torch.int64)
+            _native.call("m2f_image_views_sum", *common, out.shape[2], out.shape[3], sums.data_ptr(), sums.numel(),
+                         _native.stream(dev))
+        _native.call("m2f_image_views_color", *common, _native.ptr(sums), *store)
+        del sums
     del keep
 
 
@@ -382,14 +426,17 @@ def image_views(images, views, *, pixel_mean=None, pixel_std=None, out_dtype, si
     for i, v in enumerate(plan.views):
         img = images[v.source].numpy()
         r = _resize_bilinear_np(img[:, ::-1] if v.flip_in else img, plan.rows[i, 4:6])
-        canvas = torch.from_numpy(np.ascontiguousarray(_place_np(r, plan.rows[i], int(v.fill), True)))
+        canvas = np.ascontiguousarray(_place_np(r, plan.rows[i], int(v.fill), True))
+        if v.color is not None and v.color.ops:
+            _color_np(canvas, r.shape[:2], plan.rows[i], v.color)
+        canvas = torch.from_numpy(canvas)
         out[i, :, :canvas.shape[1], :canvas.shape[2]] = _norm_torch(canvas, mean, std, out_dtype)
     return out, list(plan.sizes)
 
 
 def _launch_label(src_ptr, elem_bytes, src_numel, plan, rows, out):
     dev = out.device
-    keep, rows_dev, tables_dev = _upload(_with_rows(plan, rows), dev)
+    keep, rows_dev, tables_dev, _ = _upload(_with_rows(plan, rows), dev)
     _native.call("m2f_label_views", src_ptr, elem_bytes, src_numel, _host_ptr(rows), rows_dev, rows.shape[0],
                  out.shape[1], tables_dev, plan.tables.size, out.data_ptr(), out.shape[2], out.shape[3],
                  _native.stream(dev))
@@ -416,7 +463,7 @@ def label_views(planes, views, *, seg_pad, size_divisibility=0, out=None):
     info = torch.iinfo(p0.dtype)
     if not info.min <= int(seg_pad) <= info.max:
         raise ValueError(f"seg_pad {seg_pad} does not fit {p0.dtype}")
-    views = [dataclasses.replace(v, fill=0) for v in views]
+    views = [dataclasses.replace(v, fill=0, color=None) for v in views]
     plan = _Plan(views, [tuple(p.shape[1:]) for p in planes], image=False)
     plan.rows[:, 16] = int(seg_pad)
     Hp, Wp = plan.padded(size_divisibility)

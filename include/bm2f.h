@@ -982,9 +982,36 @@ int m2f_bits_boundary_ragged(const int32_t* words, int64_t total_words, int num_
  * pointers give M2F_EINVAL.  An unknown dtype, mean / std with a uint8 output, a ksize beyond
  * M2F_VIEW_MAX_KSIZE (a down-scale beyond 65x) and a row whose sizes are not positive or whose source, tables
  * or canvas leave src_numel, tables_numel or (out_h, out_w) give M2F_EUNSUPPORTED.  All before any HIP call.
+ *
+ * Colour stage (bm2f_amd/color_aug.py is the definition): m2f_image_views_color is m2f_image_views
+ * with photometric operations applied to every pixel that shows the image (never to fill or pad), on the three
+ * channels of the pixel together, between the vertical pass and the normalisation.
+ *   colors (V, M2F_COLOR_FIELDS) fp64, one row per view =
+ *       0 n   operations, 0 .. M2F_COLOR_MAX_OPS      1 swap   the operations see channels 2, 1, 0
+ *       2 ci  index of the one M2F_COLOR_CONTRAST operation, -1 without       3 unused
+ *       4 + 3 k, 5 + 3 k, 6 + 3 k   code, a, b of operation k:
+ *         M2F_COLOR_CONVERT     clip(fp32(p) * fp32(a) + fp32(b), 0, 255), truncated; two fp32 roundings
+ *         M2F_COLOR_SSD_SAT     OpenCV's 8-bit BGR -> HSV, S = convert(S, a, 0), HSV -> BGR
+ *         M2F_COLOR_SSD_HUE     BGR -> HSV, H = (H + int(a)) mod 180 (non-negative), HSV -> BGR
+ *         M2F_COLOR_CONTRAST    clip(a * mean + fp64(fp32(b) * fp32(p)), 0, 255), truncated; mean = sum / count in
+ *                               fp64 over the 3 channels of the pixels the view shows, after operations 0 .. ci - 1
+ *         M2F_COLOR_SATURATION  the same with gray = fma(p2, 0.114, fma(p1, 0.587, p0 * 0.299)) in fp64 for mean
+ *   hsv_offset   element offset in `tables` of sdiv[256] then hdiv[256] (OpenCV's division tables); read only when a
+ *                view has an SSD_SAT or SSD_HUE operation, else it may be -1
+ *   sums         (V) int64 in device memory, what m2f_image_views_sum wrote; read only for views with ci >= 0 and
+ *                required (non-null) when there is one
+ *   m2f_image_views_sum   per view with ci >= 0 the exact integer sum the mean is formed from, to workspace[v]
+ *                (the host never needs it): per-workgroup partial sums in workspace[V ..], then one fixed-order
+ *                reduction per view; integer arithmetic throughout, so the result is bitwise repeatable.
+ *                m2f_image_views_sum_workspace gives the int64 words it needs.
+ * Rows of `colors` are checked like rows of `views` (M2F_EUNSUPPORTED names the row): n, ci and the codes must be the
+ * integers above, a and b finite, |a| <= 2^20 for SSD_HUE.
  * ------------------------------------------------------------------------------------------- */
 enum { M2F_U8 = 3 };
 enum { M2F_VIEW_FIELDS = 20, M2F_VIEW_MAX_KSIZE = 131 };
+enum { M2F_COLOR_FIELDS = 16, M2F_COLOR_MAX_OPS = 4 };
+enum { M2F_COLOR_CONVERT = 1, M2F_COLOR_SSD_SAT = 2, M2F_COLOR_SSD_HUE = 3, M2F_COLOR_CONTRAST = 4,
+       M2F_COLOR_SATURATION = 5 };
 int m2f_image_views(const void* src, int64_t src_numel, const int64_t* views_host, const int64_t* views_dev,
                     int num_views, const int32_t* tables, int64_t tables_numel, int normalize, float mean0,
                     float mean1, float mean2, float std0, float std1, float std2, float pad_value, int out_dtype,
@@ -992,6 +1019,16 @@ int m2f_image_views(const void* src, int64_t src_numel, const int64_t* views_hos
 int m2f_label_views(const void* src, int elem_bytes, int64_t src_numel, const int64_t* views_host,
                     const int64_t* views_dev, int num_views, int num_planes, const int32_t* tables,
                     int64_t tables_numel, void* out, int out_h, int out_w, void* stream);
+int m2f_image_views_color(const void* src, int64_t src_numel, const int64_t* views_host, const int64_t* views_dev,
+                          int num_views, const int32_t* tables, int64_t tables_numel, const double* colors_host,
+                          const double* colors_dev, int64_t hsv_offset, const int64_t* sums, int normalize,
+                          float mean0, float mean1, float mean2, float std0, float std1, float std2, float pad_value,
+                          int out_dtype, void* out, int out_h, int out_w, void* stream);
+int m2f_image_views_sum_workspace(const int64_t* views_host, int num_views, int out_h, int out_w, int64_t* words);
+int m2f_image_views_sum(const void* src, int64_t src_numel, const int64_t* views_host, const int64_t* views_dev,
+                        int num_views, const int32_t* tables, int64_t tables_numel, const double* colors_host,
+                        const double* colors_dev, int64_t hsv_offset, int out_h, int out_w, int64_t* workspace,
+                        int64_t workspace_words, void* stream);
 
 #ifdef __cplusplus
 }
