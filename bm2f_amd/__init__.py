@@ -24,6 +24,9 @@ from .image_views import (DeviceTTAMapper, View, image_views, label_views, lsj_v
 from .color_aug import ColorAug, draw_color_aug_ssd, draw_video_photometric  # noqa: F401
 from .train_mappers import (PanopticTrainMapper, SemanticTrainMapper, semantic_train_view,  # noqa: F401
                             video_clip_views)
+from .instance_views import bit_boxes_ragged, instance_views  # noqa: F401
+from .instance_mappers import (COCOInstanceLSJMapper, InstanceTrainMapper,  # noqa: F401
+                               VideoInstanceTrainMapper, sample_clip_frames, transform_polygons)
 from .sem_seg_eval import SemSegEvaluator, evaluate_sem_seg, sem_seg_metrics  # noqa: F401
 from .polygon import (ann_to_rle, convert_polygons_to_rle, polygon_crossings, polygons_to_bits,  # noqa: F401
                       polygons_to_bits_ragged, polygons_to_rle)

@@ -139,6 +139,8 @@ _SIGNATURES = {
                               _i, _p],
     "m2f_image_views_sum_workspace": [_p, _i, _i, _i, _p],
     "m2f_image_views_sum": [_p, _l, _p, _p, _i, _p, _l, _p, _p, _l, _i, _i, _p, _l, _p],
+    "m2f_bits_views_workspace": [_i, _i, _p],
+    "m2f_bits_views": [_p, _l, _p, _p, _i, _p, _l, _p, _p, _i, _i, _p, _i, _i, _p, _p, _l, _p],
 }
 
 

@@ -23,10 +23,10 @@ costs one more launch before it (``m2f_image_views_sum``, the view's exact integ
 With every ``color`` left None the call is ``m2f_image_views`` exactly as before.  The colour definitions have not
 been run against cv2 or detectron2.
 
-Out of scope: reading files, rotation (``cv2.warpAffine``), source-space ``T.RandomCrop`` of the video mappers,
-polygon annotations, the retry loop of ``RandomCrop_CategoryAreaConstraint`` (pass the chosen window as ``View.crop``),
-polygon-space transforms (rasterise with :mod:`bm2f_amd.polygon` at the output size instead) and the resize of
-float images (detectron2 uses ``F.interpolate`` there, not PIL).
+Instance annotations (RLE, arrays and polygons) under the same views are :mod:`bm2f_amd.instance_views` and
+:mod:`bm2f_amd.instance_mappers`.  Out of scope: reading files, rotation (``cv2.warpAffine``), source-space
+``T.RandomCrop`` of the video mappers, the retry loop of ``RandomCrop_CategoryAreaConstraint`` (pass the chosen window
+as ``View.crop``) and the resize of float images (detectron2 uses ``F.interpolate`` there, not PIL).
 """
 from __future__ import annotations
 

@@ -16,7 +16,8 @@ reference's augmentation lists, not the bit stream of detectron2's ``random`` / 
 never run against this module.  ``SINGLE_CATEGORY_MAX_AREA`` is 1.0 in every config of the reference, so
 ``RandomCrop_CategoryAreaConstraint`` is a plain random crop and its retry loop is not restated (a value below 1.0
 is refused).  Out of scope as well: rotation (``cv2.warpAffine``), the video mappers' source-space ``T.RandomCrop``,
-vertical flips, reading files and polygon annotations.
+vertical flips and reading files.  Instance annotations (polygons, RLE, arrays) and the instance and video-instance
+mappers are in :mod:`bm2f_amd.instance_mappers`.
 """
 from __future__ import annotations
 

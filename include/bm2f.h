@@ -1030,6 +1030,46 @@ int m2f_image_views_sum(const void* src, int64_t src_numel, const int64_t* views
                         const double* colors_dev, int64_t hsv_offset, int out_h, int out_w, int64_t* workspace,
                         int64_t workspace_words, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Instance views (bm2f_amd/instance_views.py): the views above applied to one-bit-per-pixel instance
+ * masks, a ragged number per image, with the tight box and the area of every output mask.  It restates
+ * transform_instance_annotations on a decoded mask (PIL NEAREST resize, crop, flip, zero pad) followed by
+ * BitMasks.get_bounding_boxes and a pixel count.
+ *
+ *   words   (total_words) int32, the flat buffer of m2f_rle_decode_bits_ragged / m2f_poly_decode_bits_ragged: mask m
+ *           is H x ceil(W / 32) words at its word offset, bit x % 32 of word x / 32.  Set tail bits (x >= W) and the
+ *           words between planes are ignored.
+ *   views, tables, views_host / views_dev   the view table of m2f_label_views (label axes: `tables` holds source
+ *           indices).  Fields 0, 3, 16 and 17 (source offset, strides, fill) are not read, but are checked as rows of
+ *           a source of unbounded length: pass 0, W, 0, 0.
+ *   masks   (M, M2F_BITS_VIEW_MASK_FIELDS) int64, one row per mask = 0 word offset, 1 H, 2 W, 3 view index.  H and W
+ *           must be those of the view's row.  masks_host / masks_dev as for the views.
+ *   Output pixel (y, x) of mask m under its view:  y >= Hc or x >= Wc: 0.  Else with ry = cy0 + y and rx = cx0 +
+ *           (flip_out ? cw - 1 - x : x): the source bit (taby[ry], flip_in ? W - 1 - tabx[rx] : tabx[rx]) when y < ch,
+ *           x < cw, 0 <= ry < rh and 0 <= rx < rw, else 0.
+ *   out     out_form M2F_BITS_VIEW_BITS: (M, out_h, ceil(out_w / 32)) int32 bit planes, tail bits zero;
+ *           M2F_BITS_VIEW_BYTES: (M, out_h, out_w) uint8, 0 or 1.  Every word or byte is stored exactly once.
+ *   stats   (M, 5) int32 = x0, y0, x1, y1, area of the output mask, x1 and y1 exclusive: the first and last set
+ *           column and row (+ 1) and the number of set pixels; an empty mask gives five zeros.
+ *   workspace   int32 words, m2f_bits_views_workspace(num_masks, out_h) of them: a workgroup owns
+ *           M2F_BITS_VIEW_BAND_ROWS rows of one mask's plane (workgroup b: mask b / bands, band b % bands, bands =
+ *           ceil(out_h / M2F_BITS_VIEW_BAND_ROWS)) and writes its partial stats there; a second kernel reduces each
+ *           mask's partials in band order.  Two launches whatever M and V are; no atomics, no memset; integer
+ *           arithmetic throughout, so out and stats are bitwise repeatable.
+ * Null pointers, non-positive counts, misaligned pointers, an unknown out_form or a workspace that is too small
+ * give M2F_EINVAL.  More than 2^31 - 1 words in or out (bytes / 4 for the uint8 form), out_h * out_w or H * W beyond
+ * 2^31 - 1, a view row as for m2f_label_views, and a mask row whose view is out of range, whose size is not positive
+ * or not the view's, or whose plane leaves the buffer give M2F_EUNSUPPORTED naming the row.  All before any HIP
+ * call.  The kernel repeats the row checks on the device copies and writes zeros for a mask that fails them.
+ * ------------------------------------------------------------------------------------------- */
+enum { M2F_BITS_VIEW_MASK_FIELDS = 4, M2F_BITS_VIEW_BAND_ROWS = 32 };
+enum { M2F_BITS_VIEW_BITS = 0, M2F_BITS_VIEW_BYTES = 1 };
+int m2f_bits_views_workspace(int num_masks, int out_h, int64_t* words);
+int m2f_bits_views(const int32_t* words, int64_t total_words, const int64_t* views_host, const int64_t* views_dev,
+                   int num_views, const int32_t* tables, int64_t tables_numel, const int64_t* masks_host,
+                   const int64_t* masks_dev, int num_masks, int out_form, void* out, int out_h, int out_w,
+                   int32_t* stats, int32_t* workspace, int64_t workspace_words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
