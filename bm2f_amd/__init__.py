@@ -8,7 +8,10 @@ from . import _native  # noqa: F401
 from .inference import (MaskFormerInference, instance_inference, panoptic_inference,  # noqa: F401
                         semantic_inference)
 from .mask_criterion import HungarianMatcher, SetCriterion, VideoHungarianMatcher, VideoSetCriterion  # noqa: F401
-from .evaluation import instances_to_coco_json, instances_to_coco_json_video  # noqa: F401
+from .evaluation import (instance_map_annotations, instances_to_coco_json,  # noqa: F401
+                         instances_to_coco_json_video, load_sem_seg_predictions, panoptic_to_coco_detection,
+                         sem_seg_to_coco_json)
+from .label_rle import label_maps_to_rle, rle_to_label_maps  # noqa: F401
 from .coco_eval import (COCOEvalResult, COCOEvaluator, COCOGroundTruth, COCOParams,  # noqa: F401
                         evaluate_coco)
 from .mask_iou import (mask_iou, mask_pair_counts, mask_pair_counts_ragged, rle_to_bits,  # noqa: F401

@@ -141,6 +141,12 @@ _SIGNATURES = {
     "m2f_image_views_sum": [_p, _l, _p, _p, _i, _p, _l, _p, _p, _l, _i, _i, _p, _l, _p],
     "m2f_bits_views_workspace": [_i, _i, _p],
     "m2f_bits_views": [_p, _l, _p, _p, _i, _p, _l, _p, _p, _i, _i, _p, _i, _i, _p, _p, _l, _p],
+    "m2f_label_rle_col_counts": [_p, _i, _l, _i, _p, _l, _p],
+    "m2f_label_rle_runs": [_p, _i, _l, _i, _p, _l, _p, _p, _l, _p],
+    "m2f_label_rle_spans": [_p, _p, _l, _p, _p, _p, _i, _p, _p, _l, _p, _p, _p, _p, _p],
+    "m2f_label_rle_seg_keys": [_p, _p, _p, _l, _p, _l, _p, _p],
+    "m2f_label_rle_segments": [_p, _l, _p, _p, _p, _p, _p, _i, _p, _p, _l, _p, _l, _p, _p, _p],
+    "m2f_rle_paint_labels": [_p, _l, _p, _l, _p, _p, _i, _l, _l, _i, _p, _l, _p],
 }
 
 

@@ -100,9 +100,19 @@ class SemSegEvaluator:
 
     A ground-truth label outside ``[0, num_classes)`` that is not ``ignore_label``, or a predicted label outside
     ``[0, num_classes)``, raises ValueError naming the image (the table's last prediction column exists only to keep
-    it square and must stay empty)."""
+    it square and must stay empty).
 
-    def __init__(self, num_classes, ignore_label, class_names=None, device=None, with_pq=False):
+    With ``output_dir`` or ``keep_predictions`` ``process`` also collects detectron2's ``sem_seg_predictions.json``
+    entries (:func:`bm2f_amd.evaluation.sem_seg_to_coco_json`, one more call per batch; ``file_name`` is the input's
+    ``file_name``, else its ``sem_seg_file_name`` or ``image_id``; ``contiguous_id_to_dataset_id`` maps the category
+    ids); ``evaluate`` writes them to ``output_dir/sem_seg_predictions.json`` and they stay in ``predictions``.  With
+    both left at their defaults nothing is collected and no extra launch runs."""
+
+    def __init__(self, num_classes, ignore_label, class_names=None, device=None, with_pq=False, output_dir=None,
+                 keep_predictions=False, contiguous_id_to_dataset_id=None):
+        self.output_dir = output_dir
+        self.keep_predictions = bool(keep_predictions)
+        self.contiguous_id_to_dataset_id = contiguous_id_to_dataset_id
         self.num_classes = int(num_classes)
         self.ignore_label = int(ignore_label)
         if self.num_classes < 1:
@@ -120,6 +130,7 @@ class SemSegEvaluator:
         self._counts = np.zeros((n, n), dtype=np.int64)               # [gt row, pred column], as the kernel counts
         self.pq_stat = PQStat(sorted(self.categories)) if self.with_pq else None
         self.num_images = 0
+        self.predictions = []                                         # the entries of sem_seg_predictions.json
 
     @property
     def conf_matrix(self):
@@ -192,7 +203,17 @@ class SemSegEvaluator:
             for k, table in enumerate(tables):
                 self._counts += table
                 self.pq_stat += self.image_pq(table, self._name(inputs[k], k))
+        if self.output_dir is not None or self.keep_predictions:
+            from .evaluation import sem_seg_to_coco_json             # one more call per batch, only when asked for
+            self.predictions += sem_seg_to_coco_json(preds, [self._file_name(inp, k) for k, inp in enumerate(inputs)],
+                                                     contiguous_id_to_dataset_id=self.contiguous_id_to_dataset_id)
         self.num_images += len(inputs)
+
+    def _file_name(self, inp, k):
+        for key in ("file_name", "sem_seg_file_name", "image_id"):
+            if key in inp:
+                return str(inp[key])
+        return str(self.num_images + k)
 
     def image_pq(self, table, image_id=None):
         """One image's (K + 1, K + 1) table ``[gt, pred]`` -> its PQStat by the rules of the reference tool."""
@@ -208,6 +229,12 @@ class SemSegEvaluator:
         ``with_pq`` also ``"PQ"``, ``"SQ"``, ``"RQ"``, ``"PQ-<name>"``, ``"SQ-<name>"``, ``"RQ-<name>"`` x 100 and
         ``"pq_stats"``, the per-class ``tp``, ``fp``, ``fn``, ``iou``."""
         res = sem_seg_metrics(self.conf_matrix, self.class_names)
+        if self.output_dir is not None:
+            import json
+            import os
+            os.makedirs(self.output_dir, exist_ok=True)
+            with open(os.path.join(self.output_dir, "sem_seg_predictions.json"), "w") as f:
+                f.write(json.dumps(self.predictions))
         if self.with_pq:
             avg, per_class = self.pq_stat.pq_average(self.categories)
             for key in ("pq", "sq", "rq"):

@@ -1070,6 +1070,70 @@ int m2f_bits_views(const int32_t* words, int64_t total_words, const int64_t* vie
                    const int64_t* masks_dev, int num_masks, int out_form, void* out, int out_h, int out_w,
                    int32_t* stats, int32_t* workspace, int64_t workspace_words, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * COCO RLE of the segments of label maps, and its inverse (bm2f_amd/label_rle.py): what
+ * detectron2's encode_json_sem_seg, datasets/prepare_ade20k_ins_seg.py and the panoptic-to-detection conversion get
+ * from pycocotools.mask.encode(map == v) once per value, without a dense mask per segment.  A label map read
+ * column-major (p = x * H + y) is a sequence of runs of one label; the segment `map == v` has the transitions s and,
+ * when e < H * W, e of every run [s, e) of v, and the RLE format is that of m2f_rle_* above.
+ *
+ *   images (B, M2F_LABEL_RLE_IMAGE_FIELDS) int64, device = 0 address of pixel (0, 0) of the plane (label_bytes 1 =
+ *           uint8, 2 = int16, 4 = int32 elements, unit column stride), 1 H, 2 W (both > 0, H * W < 2^31), 3 row stride
+ *           in elements, 4 col_base (running sum of W), 5 block_base (running sum of ceil(W / 256)), 6 the key of the
+ *           label whose pixels belong to no segment or -1, 7 unused.  The key of (image i, label v) is
+ *           (i << 32) | (uint32(v) ^ 0x80000000): int64 order is (image, signed label).  The planes are read through
+ *           the addresses of the table, which the entry points cannot check: they are the caller's.
+ *   m2f_label_rle_col_counts  counts (total_cols) int32: the runs that start in column col_base + x (a run starts
+ *           where a label differs from the pixel before it in column-major order; pixel 0 starts one).  Grid =
+ *           num_blocks = sum ceil(W / 256).
+ *   m2f_label_rle_runs        col_start = exclusive scan of counts.  run_pos[o] int32 / run_key[o] int64 = start and
+ *           key of run o; a slot at or beyond `capacity` is never written.
+ *   The caller sorts run_key stably (sorted_key, perm): runs of one segment become adjacent, in position order.
+ *   m2f_label_rle_spans       per sorted run j: start[j], end[j] (the next run of its image, run_base (B + 1) int64
+ *           being the images' first runs, or H * W), ntrans[j] = 0 when the label is no segment (the ignore key, or
+ *           absent from seg_key when seg_key is given), else 1 + (end < H * W); first[j] = 1 on the first run of a
+ *           segment.
+ *   m2f_label_rle_seg_keys    seg_rank = inclusive scan of first: seg_key[seg_rank[j] - 1] = sorted_key[j] where
+ *           first[j], *num_segments = seg_rank[num_runs - 1] (both capped by seg_capacity).  Not called when the
+ *           caller supplies seg_key (ascending) and *num_segments itself.
+ *   m2f_label_rle_segments    tscan = inclusive scan of ntrans.  One wave per segment slot s <= seg_capacity.  For s <
+ *           *num_segments: the transitions of its runs and the closing H * W go to positions[seg_start[s] + s ...],
+ *           seg_start[s] = the transitions of all runs before its first; headers[s] (M2F_LABEL_RLE_HEADER_FIELDS
+ *           int32) = image, label, area, xmin, ymin, xmax, ymax (0, 0, -1, -1 when empty), H * W.  A run that
+ *           crosses a column boundary spans rows 0 .. H - 1.  For s >= *num_segments: seg_start[s] = tscan[last],
+ *           headers zero, nothing else: with `positions` zeroed on entry these are one-entry dummies, so that
+ *           m2f_rle_deltas / m2f_rle_chars run on (positions, seg_start, seg_capacity + 1, width 1, capacity) although
+ *           the number of segments is known on the device only.
+ *   m2f_rle_paint_labels      the inverse.  positions / total / offsets (num_segments + 1) as m2f_rle_decode_bits;
+ *           values (num_segments) int32; images (B, M2F_LABEL_RLE_PAINT_FIELDS) int64 = 0 H, 1 W, 2 first segment,
+ *           3 end segment, 4 element offset of the plane in out, 5 block_base (running sum of ceil(W / 64) *
+ *           ceil(H / 4)).  out[offset + y * W + x] = values[s] of the last segment s of the image with an odd number
+ *           of run ends <= x * H + y, else fill: later segments overwrite earlier ones.  A lane owns one pixel, a
+ *           wave 64 consecutive x of one row; one launch, every element stored once, no atomics, no memset.
+ * Null pointers, negative sizes, misaligned tables and a label_bytes other than 1, 2, 4 give M2F_EINVAL; more than
+ * 2^31 - 1 workgroups M2F_EUNSUPPORTED; all before any HIP call.  The kernels check every index they take from a
+ * device table against the sizes passed by value.
+ * ------------------------------------------------------------------------------------------- */
+enum { M2F_LABEL_RLE_IMAGE_FIELDS = 8, M2F_LABEL_RLE_HEADER_FIELDS = 8, M2F_LABEL_RLE_PAINT_FIELDS = 6 };
+int m2f_label_rle_col_counts(const int64_t* images, int num_images, int64_t num_blocks, int label_bytes,
+                             int32_t* counts, int64_t total_cols, void* stream);
+int m2f_label_rle_runs(const int64_t* images, int num_images, int64_t num_blocks, int label_bytes,
+                       const int64_t* col_start, int64_t total_cols, int32_t* run_pos, int64_t* run_key,
+                       int64_t capacity, void* stream);
+int m2f_label_rle_spans(const int64_t* sorted_key, const int64_t* perm, int64_t num_runs, const int32_t* run_pos,
+                        const int64_t* run_base, const int64_t* images, int num_images, const int64_t* seg_key,
+                        const int64_t* num_segments, int64_t seg_capacity, int32_t* start, int32_t* end,
+                        int32_t* ntrans, int32_t* first, void* stream);
+int m2f_label_rle_seg_keys(const int64_t* sorted_key, const int32_t* first, const int64_t* seg_rank, int64_t num_runs,
+                           int64_t* seg_key, int64_t seg_capacity, int64_t* num_segments, void* stream);
+int m2f_label_rle_segments(const int64_t* sorted_key, int64_t num_runs, const int32_t* start, const int32_t* end,
+                           const int32_t* ntrans, const int64_t* tscan, const int64_t* images, int num_images,
+                           const int64_t* seg_key, const int64_t* num_segments, int64_t seg_capacity,
+                           int32_t* positions, int64_t capacity, int64_t* seg_start, int32_t* headers, void* stream);
+int m2f_rle_paint_labels(const int32_t* positions, int64_t total, const int64_t* offsets, int64_t num_segments,
+                         const int32_t* values, const int64_t* images, int num_images, int64_t num_blocks,
+                         int64_t fill, int label_bytes, void* out, int64_t out_elems, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
