@@ -4,7 +4,8 @@ The reference runs the pixel decoder with autocast off (msdeformattn.py:314,320)
 projections / lateral conv / mask_features conv and the 3x3 output conv are fp32 convs on the vendor
 library (reference: cuDNN, :213-292).  Here forward and input gradient are implicit GEMMs with the
 weights split exactly into three bf16 planes and the activations split in registers (fp32-accurate, see
-csrc/gemm_x3.hip), the weight gradient a split-over-pixels GEMM with its slabs summed in a fixed order.
+csrc/gemm_x3.hip), the weight gradient a split-over-pixels GEMM with its slabs summed in a fixed order (3x3: one
+tap-fused kernel, ``WGRAD3``).
 CUDA fp32 NCHW inputs that meet the kernel's shape rules run here (a missing library raises); anything
 else uses ``F.conv2d``.
 """
@@ -17,11 +18,15 @@ from torch.autograd import Function
 from . import _native
 
 
-# 3x3 weight-gradient engine (tools/conv_bench.py, bs16 256x256x256, wgrad share of the backward):
-#   "tn"     nine x3 TN GEMMs over zero-bordered pixel-row copies of dO and I (_wgrad3_tn): ~9.4 ms
-#   "miopen" fp32 igemm_wrw on its own NHWC transposes: ~10.1 ms
-#   "x3"     the implicit-GEMM kernel of csrc/conv_x3.hip on NCHW (channel-strided operands): ~14 ms
-WGRAD3 = "tn"   # 3x3 weight gradient: "tn" (x3 TN GEMMs per tap) or "miopen"; set by tools / tests
+# 3x3 weight-gradient engine (tools/conv_bench.py, bs16 256x256x256, weight gradient alone, four alternated rounds,
+# profiles/wgrad3_conv_bench_ab.txt; the forward kernel, the MFMA floor of this product, takes 5.6-5.9 ms there):
+#   "fused"  one tap-fused x3 kernel on the NCHW operands (wgrad3_fused), each operand read and split once per
+#            staged tile: 6.15-6.18 ms
+#   "tn"     nine x3 TN GEMMs over zero-bordered pixel-row copies of dO and I (_wgrad3_tn): 7.39-7.44 ms
+#   "miopen" fp32 igemm_wrw on its own NHWC transposes: 10.2 ms
+#   "x3"     the implicit-GEMM kernel of csrc/conv_x3.hip on NCHW (channel-strided operands): 12.8 ms
+# In the step "fused" is 1.06 ms faster than "tn" (four alternated pairs, every pair; profiles/wgrad3_step_ab.txt).
+WGRAD3 = "fused"   # 3x3 weight gradient engine: "fused", "tn", "miopen" or "x3"; set by tools / tests
 
 
 def _workspace(N, Ci, Co, H, W, k, device):
@@ -93,6 +98,9 @@ class Conv2dX3(Function):
         if k == 3 and WGRAD3 == "tn" and ctx.needs_input_grad[1]:
             dw = _wgrad3_tn(g, x)
             db = g.sum((2, 3)).sum(0) if want_b else None   # two reductions with many outputs (graph-safe)
+        elif k == 3 and WGRAD3 == "fused" and (ctx.needs_input_grad[1] or want_b):
+            dw, db = wgrad3_fused(g, x, want_b)
+            dw = dw if ctx.needs_input_grad[1] else None
         elif k == 3 and WGRAD3 == "miopen" and (ctx.needs_input_grad[1] or want_b):
             # 3x3 weight gradient on the library (WGRAD3 = "miopen")
             _, dw, db = torch.ops.aten.convolution_backward(
@@ -105,6 +113,21 @@ class Conv2dX3(Function):
                          H, W, k, ws.data_ptr(), ws.numel(), _native.stream(g))
             dw = tck.permute(2, 1, 0).reshape(Co, Ci, k, k) if ctx.needs_input_grad[1] else None
         return dx, dw, db
+
+
+def wgrad3_fused(g, x, want_bias, splits=0):
+    """3x3 "same" conv weight gradient (Co, Ci, 3, 3) and, if wanted, bias gradient (Co,) of contiguous fp32 NCHW
+    ``g`` = dO and ``x`` in the tap-fused kernel (csrc/conv_x3.hip: one pass over both operands, all nine taps per
+    staged tile).  ``splits`` > 0 forces the number of pixel slabs (0: chosen by the library)."""
+    N, Ci, H, W = x.shape
+    Co = g.shape[1]
+    ws = _native.workspace("m2f_conv_f32x3_wgrad3_fused_workspace", N, Ci, Co, H, W, splits, device=x.device,
+                           floor=16)
+    dw = torch.empty(Co, Ci, 3, 3, device=x.device, dtype=torch.float32)
+    db = torch.empty(Co, device=x.device, dtype=torch.float32) if want_bias else None
+    _native.call("m2f_conv_f32x3_wgrad3_fused", g.data_ptr(), x.data_ptr(), dw.data_ptr(), _native.ptr(db), N, Ci,
+                 Co, H, W, splits, ws.data_ptr(), ws.numel(), _native.stream(g))
+    return dw, db
 
 
 def _pad_nhwc(t):

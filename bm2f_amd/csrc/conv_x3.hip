@@ -14,6 +14,8 @@
 // (slabs reduced in a fixed order, deterministic): the (tap, ci) side is wave-direct (8 consecutive
 // pixels of one shifted channel per lane), dO goes through LDS (a thread owns one channel x 8 pixels:
 // two float4 loads), bias gradient = channel sums of dO taken while staging.
+// The 3x3 weight gradient also has a tap-fused form (x3_conv_wgrad3_fused_kernel): both operands through
+// LDS, each split once per staged tile, all nine taps from the same staged planes.
 #include "bm2f.h"
 #include "common.h"
 #include "x3_device.h"
@@ -533,6 +535,216 @@ __global__ void __launch_bounds__(256) x3_conv_slab_reduce(const float* __restri
   out[i] = (a0 + a1) + (a2 + a3);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// tap-fused 3x3 weight gradient on NCHW operands as autograd hands them over (no padded copies, no
+// transposes): dW[co][ci][dy+1][dx+1] = sum_{n,y,x} dO[n][co][y][x] . I[n][ci][y+dy][x+dx].
+// The contraction runs over pixels and both operands are pixel-contiguous per channel, i.e. K-major.
+// A block owns 128 co x 32 ci x all nine taps over a slab of chunks; a chunk is 4 image rows x 8 pixels.
+// Per chunk it stages the 4 dO segments of each co and the 6 I segments (rows y0-1 .. y0+4, pixels
+// x0-1 .. x0+8, zero outside the image) of each ci: every staged value is split into its three bf16 planes
+// once (split_pairs: split8's arithmetic), the dx = -1 / 0 / +1 windows of an I segment are three aligned
+// 16-byte LDS rows cut from the same five packed words (dx = 0 by one funnel shift per word), and row r of
+// I serves dy = +1 / 0 / -1 of the dO rows r-2 / r-1 / r.  A wave (32 co x 32 ci) then runs 2 K-steps of 16
+// pixels (lane half = one of two rows) x 9 taps x 6 products into nine accumulator tiles (144 registers).
+// Slabs over chunk ranges land in slab[split][co][ci][tap] (the layout of the result) and are summed in a
+// fixed order by x3_conv_slab_reduce; the bias gradient is the channel sums of dO taken while staging.
+// LDS: I 6 x 9 x 32 x 16 B + dO 4 x 3 x 128 x 16 B = 52,224 B, single-buffered: two blocks per CU (register
+// bound, <= 256 per lane) take turns staging and multiplying.
+// ---------------------------------------------------------------------------------------------------
+constexpr int kF_CO = 128, kF_CI = 32, kF_R = 4;
+
+// split3 of NP consecutive pairs, packed (element 0 of a pair in the low half): the arithmetic of split8
+template <int NP>
+__device__ __forceinline__ void split_pairs(const float* x, unsigned* h, unsigned* m, unsigned* l) {
+  using b2 = __bf16 __attribute__((ext_vector_type(2)));
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const float x0 = x[2 * p], x1 = x[2 * p + 1];
+    const unsigned hp = __builtin_bit_cast(unsigned, b2{static_cast<__bf16>(x0), static_cast<__bf16>(x1)});
+    float r0 = x0 - __uint_as_float(hp << 16), r1 = x1 - __uint_as_float(hp & 0xffff0000u);
+    r0 = r0 == r0 ? r0 : 0.f;
+    r1 = r1 == r1 ? r1 : 0.f;
+    const unsigned mp = __builtin_bit_cast(unsigned, b2{static_cast<__bf16>(r0), static_cast<__bf16>(r1)});
+    const float s0 = r0 - __uint_as_float(mp << 16), s1 = r1 - __uint_as_float(mp & 0xffff0000u);
+    h[p] = hp;
+    m[p] = mp;
+    l[p] = __builtin_bit_cast(unsigned, b2{static_cast<__bf16>(s0), static_cast<__bf16>(s1)});
+  }
+}
+
+__global__ void __launch_bounds__(256, 2) x3_conv_wgrad3_fused_kernel(const float* __restrict__ dO,
+                                                                      const float* __restrict__ I, int N, int Co,
+                                                                      int Ci, int H, int W, int chunks_per_split,
+                                                                      float* __restrict__ slab,
+                                                                      float* __restrict__ bias_slab) {
+  using u4 = unsigned __attribute__((ext_vector_type(4)));
+  constexpr int NI = (kF_R + 2) * 9 * kF_CI, NO = kF_R * 3 * kF_CO;   // 16-byte rows
+  __shared__ __attribute__((aligned(16))) u4 smem[NI + NO];
+  u4* sI = smem;        // [row 0..5][dx 0..2][plane][ci]
+  u4* sO = smem + NI;   // [row 0..3][plane][co]
+
+  const int HW = H * W, WS = W / 8, HB = (H + kF_R - 1) / kF_R;
+  const int NQ = N * HB * WS;
+  const int nco = (Co + kF_CO - 1) / kF_CO, nci = (Ci + kF_CI - 1) / kF_CI, tiles = nco * nci;
+  const int id = xcd_remap(blockIdx.x, gridDim.x);
+  const int split = id / tiles, t = id % tiles;
+  const int co0 = (t % nco) * kF_CO, ci0 = (t / nco) * kF_CI;
+  const int q0 = min(split * chunks_per_split, NQ), q1 = min(q0 + chunks_per_split, NQ);
+  const int nk = q1 - q0;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int li = lane & 31, lh = lane >> 5;
+  const bool csum = bias_slab != nullptr && ci0 == 0;
+
+  // staging jobs of a thread: dO (channel tid % 128, rows tid / 128 and tid / 128 + 2); threads 0..191 also
+  // I (channel tid % 32, staged row tid / 32)
+  const int oc = tid & (kF_CO - 1), orow = tid >> 7;
+  const int ic = tid & (kF_CI - 1), irow = tid >> 5;
+  const bool ijob = irow < kF_R + 2;
+  const int64_t obase = static_cast<int64_t>(min(co0 + oc, Co - 1)) * HW;
+  const int64_t ibase = static_cast<int64_t>(min(ci0 + ic, Ci - 1)) * HW;
+
+  struct Regs {
+    f4 o[2][2];
+    f4 i[2];
+    float il, ir;
+  };
+  auto coords = [&](int c, int& n, int& y0, int& x0) {
+    const int q = q0 + c, tq = q / WS;
+    x0 = (q - tq * WS) * 8;
+    n = tq / HB;
+    y0 = (tq - n * HB) * kF_R;
+  };
+  auto gload = [&](Regs& r, int c) {
+    int n, y0, x0;
+    coords(c, n, y0, x0);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int y = min(y0 + orow + 2 * u, H - 1);
+      const float* src = dO + static_cast<int64_t>(n) * Co * HW + obase + y * W + x0;
+      r.o[u][0] = *reinterpret_cast<const f4*>(src);
+      r.o[u][1] = *reinterpret_cast<const f4*>(src + 4);
+    }
+    if (ijob) {
+      const int y = min(max(y0 + irow - 1, 0), H - 1);
+      const float* row = I + static_cast<int64_t>(n) * Ci * HW + ibase + y * W;
+      r.i[0] = *reinterpret_cast<const f4*>(row + x0);
+      r.i[1] = *reinterpret_cast<const f4*>(row + x0 + 4);
+      r.il = row[max(x0 - 1, 0)];
+      r.ir = row[min(x0 + 8, W - 1)];
+    }
+  };
+  float csb = 0.f;
+  auto stage = [&](const Regs& r, int c) {
+    int n, y0, x0;
+    coords(c, n, y0, x0);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int rr = orow + 2 * u;
+      const bool ok = y0 + rr < H;
+      float v[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = ok ? r.o[u][e >> 2][e & 3] : 0.f;
+      if (csum) csb += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+      unsigned h[4], m[4], l[4];
+      split_pairs<4>(v, h, m, l);
+      u4* dst = sO + rr * 3 * kF_CO + oc;
+      dst[0] = u4{h[0], h[1], h[2], h[3]};
+      dst[kF_CO] = u4{m[0], m[1], m[2], m[3]};
+      dst[2 * kF_CO] = u4{l[0], l[1], l[2], l[3]};
+    }
+    if (ijob) {
+      const int yy = y0 + irow - 1;
+      const bool ok = yy >= 0 && yy < H;
+      float v[10];   // pixels x0 - 1 .. x0 + 8
+      v[0] = ok && x0 > 0 ? r.il : 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e + 1] = ok ? r.i[e >> 2][e & 3] : 0.f;
+      v[9] = ok && x0 + 8 < W ? r.ir : 0.f;
+      unsigned pl[3][5];
+      split_pairs<5>(v, pl[0], pl[1], pl[2]);
+      u4* dst = sI + irow * 9 * kF_CI + ic;
+#pragma unroll
+      for (int p = 0; p < 3; ++p) {
+        const unsigned* s = pl[p];
+        dst[(0 * 3 + p) * kF_CI] = u4{s[0], s[1], s[2], s[3]};                               // dx = -1
+        dst[(1 * 3 + p) * kF_CI] = u4{(s[0] >> 16) | (s[1] << 16), (s[1] >> 16) | (s[2] << 16),
+                                      (s[2] >> 16) | (s[3] << 16), (s[3] >> 16) | (s[4] << 16)};  // dx = 0
+        dst[(2 * 3 + p) * kF_CI] = u4{s[1], s[2], s[3], s[4]};                               // dx = +1
+      }
+    }
+  };
+
+  f16v acc[9];
+#pragma unroll
+  for (int j = 0; j < 9; ++j)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
+  auto chunk_mfma = [&]() {
+#pragma unroll
+    for (int s = 0; s < kF_R / 2; ++s) {
+      const int rr = 2 * s + lh;
+      const u4* ao = sO + rr * 3 * kF_CO + w * 32 + li;
+      bf8 fa[3];
+#pragma unroll
+      for (int p = 0; p < 3; ++p) fa[p] = __builtin_bit_cast(bf8, ao[p * kF_CO]);
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) {
+        const u4* bi = sI + ((rr + tap / 3) * 3 + tap % 3) * 3 * kF_CI + li;
+        acc[tap] = mfma_x3(fa, __builtin_bit_cast(bf8, bi[0]), __builtin_bit_cast(bf8, bi[kF_CI]),
+                           __builtin_bit_cast(bf8, bi[2 * kF_CI]), acc[tap]);
+      }
+    }
+  };
+
+  if (nk > 0) {
+    Regs r;
+    gload(r, 0);
+    for (int c = 0; c < nk; ++c) {
+      __syncthreads();   // the previous chunk's operand reads are done
+      stage(r, c);
+      __syncthreads();
+      if (c + 1 < nk) gload(r, c + 1);
+      chunk_mfma();
+    }
+  }
+
+  // tile `tap` holds C[co = (e&3) + 8(e>>2) + 4lh][ci = li]; slab[split][co][ci][tap]
+  float* out = slab + static_cast<int64_t>(split) * Co * Ci * 9;
+  const int ci = ci0 + li;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int co = co0 + w * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+    if (co < Co && ci < Ci) {
+      float* dst = out + (static_cast<int64_t>(co) * Ci + ci) * 9;
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) dst[tap] = acc[tap][e];
+    }
+  }
+  if (csum) {
+    __syncthreads();
+    float* red = reinterpret_cast<float*>(smem);
+    if (orow == 1) red[oc] = csb;
+    __syncthreads();
+    if (orow == 0 && co0 + oc < Co) bias_slab[static_cast<int64_t>(split) * Co + co0 + oc] = csb + red[oc];
+  }
+}
+
+struct FusedPlan {
+  int splits, chunks;   // slabs and chunks per slab
+};
+
+// splits_req > 0 forces the slab count (tests); else about two blocks per CU, at least 4 chunks per slab
+FusedPlan fused_plan(int N, int Ci, int Co, int H, int W, int splits_req) {
+  const int64_t NQ = static_cast<int64_t>(N) * ((H + kF_R - 1) / kF_R) * (W / 8);
+  const int tiles = ((Co + kF_CO - 1) / kF_CO) * ((Ci + kF_CI - 1) / kF_CI);
+  int64_t splits = splits_req > 0 ? splits_req : (512 + tiles - 1) / tiles;
+  const int64_t cap = splits_req > 0 ? NQ : (NQ + 3) / 4;
+  if (splits > cap) splits = cap;
+  if (splits < 1) splits = 1;
+  const int64_t chunks = (NQ + splits - 1) / splits;
+  return FusedPlan{static_cast<int>((NQ + chunks - 1) / chunks), static_cast<int>(chunks)};
+}
+
 int conv_check(const char* fn, int N, int C, int H, int W, int Co, int T) {
   if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || Co <= 0) return m2f::fail(M2F_EINVAL, "%s: bad sizes", fn);
   if (T != 1 && T != 9) return m2f::fail(M2F_EUNSUPPORTED, "%s: kernel must be 1x1 or 3x3", fn);
@@ -715,6 +927,51 @@ extern "C" int m2f_conv_f32x3_wgrad(const float* dO, const float* I, float* dW, 
                                     int H, int W, int ksize, void* workspace, int64_t workspace_bytes, void* stream) {
   return wgrad_impl("m2f_conv_f32x3_wgrad", dO, I, M2F_F32, 0, dW, dbias, N, Ci, Co, H, W, ksize, workspace,
                     workspace_bytes, stream);
+}
+
+extern "C" int m2f_conv_f32x3_wgrad3_fused_workspace(int N, int Ci, int Co, int H, int W, int splits,
+                                                     int64_t* workspace_bytes) {
+  int rc = conv_check("m2f_conv_f32x3_wgrad3_fused_workspace", N, Ci, H, W, Co, 9);
+  if (rc) return rc;
+  if (Co % 16) return m2f::fail(M2F_EUNSUPPORTED, "m2f_conv_f32x3_wgrad3_fused_workspace: out channels %% 16 != 0");
+  const FusedPlan p = fused_plan(N, Ci, Co, H, W, splits);
+  if (workspace_bytes) *workspace_bytes = static_cast<int64_t>(p.splits) * (static_cast<int64_t>(9) * Ci * Co + Co) * 4;
+  return m2f::ok();
+}
+
+// dW [Co][Ci][3][3] = sum_{n,p} dO[n][co][p] I[n][ci][p + s(tap)] in one tap-fused kernel on the NCHW operands;
+// dbias [Co] = sum dO (if dbias).  splits: 0 = chosen here, > 0 = that many pixel slabs (at most one per chunk)
+extern "C" int m2f_conv_f32x3_wgrad3_fused(const float* dO, const float* I, float* dW, float* dbias, int N, int Ci,
+                                           int Co, int H, int W, int splits, void* workspace, int64_t workspace_bytes,
+                                           void* stream) {
+  const char* fn = "m2f_conv_f32x3_wgrad3_fused";
+  int rc = conv_check(fn, N, Ci, H, W, Co, 9);
+  if (rc) return rc;
+  if (Co % 16) return m2f::fail(M2F_EUNSUPPORTED, "%s: out channels %% 16 != 0", fn);
+  if (!dO || !I || !dW || !workspace) return m2f::fail(M2F_EINVAL, "%s: null pointer", fn);
+  if (!m2f::aligned(dO, 16) || !m2f::aligned(I, 16) || !m2f::aligned(workspace, 16))
+    return m2f::fail(M2F_EINVAL, "%s: misaligned", fn);
+  if (splits < 0) return m2f::fail(M2F_EINVAL, "%s: splits %d", fn, splits);
+  const FusedPlan p = fused_plan(N, Ci, Co, H, W, splits);
+  const int64_t n = static_cast<int64_t>(9) * Ci * Co;
+  if (workspace_bytes < static_cast<int64_t>(p.splits) * (n + Co) * 4)
+    return m2f::fail(M2F_EINVAL, "%s: workspace too small", fn);
+  const int64_t tiles = static_cast<int64_t>((Co + kF_CO - 1) / kF_CO) * ((Ci + kF_CI - 1) / kF_CI);
+  if (p.splits * tiles > 0x7fffffff || static_cast<int64_t>(N) * ((H + kF_R - 1) / kF_R) * (W / 8) > 0x7fffffff)
+    return m2f::fail(M2F_EUNSUPPORTED, "%s: too many tiles", fn);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* slab = static_cast<float*>(workspace);
+  float* bslab = slab + p.splits * n;
+  x3_conv_wgrad3_fused_kernel<<<static_cast<unsigned>(p.splits * tiles), 256, 0, st>>>(
+      dO, I, N, Co, Ci, H, W, p.chunks, slab, dbias ? bslab : nullptr);
+  if ((rc = m2f::check_launch(fn))) return rc;
+  x3_conv_slab_reduce<<<m2f::ceil_div(n, 256), 256, 0, st>>>(slab, p.splits, n, dW);
+  if ((rc = m2f::check_launch(fn))) return rc;
+  if (dbias) {
+    x3_conv_slab_reduce<<<m2f::ceil_div(Co, 256), 256, 0, st>>>(bslab, p.splits, Co, dbias);
+    return m2f::check_launch(fn);
+  }
+  return m2f::ok();
 }
 
 extern "C" int m2f_conv_x3_wgrad_io(const float* dO, const void* I, int i_dtype, int i_nhwc, float* dW, float* dbias,

@@ -310,6 +310,14 @@ int m2f_conv_f32x3(const float* I, const float* W, const float* bias, float* O, 
                    int ksize, int mode, void* workspace, int64_t workspace_bytes, void* stream);
 int m2f_conv_f32x3_wgrad(const float* grad_out, const float* I, float* dW_tck, float* dbias, int N, int Ci, int Co,
                          int H, int Wd, int ksize, void* workspace, int64_t workspace_bytes, void* stream);
+/* The 3x3 weight gradient in one tap-fused kernel on the NCHW operands (no padded copies, no per-tap
+ * launches): dW[Co][Ci][3][3], the layout of the weight itself, and, if dbias, dbias[Co].  The pixels are
+ * split into slabs (splits = 0: chosen by the library; > 0: that many, at most one per 4-row x 8-pixel
+ * chunk) summed in a fixed order: bitwise repeatable.  Same shape rules as above; the workspace query
+ * takes the same splits. */
+int m2f_conv_f32x3_wgrad3_fused_workspace(int N, int Ci, int Co, int H, int Wd, int splits, int64_t* workspace_bytes);
+int m2f_conv_f32x3_wgrad3_fused(const float* grad_out, const float* I, float* dW, float* dbias, int N, int Ci, int Co,
+                                int H, int Wd, int splits, void* workspace, int64_t workspace_bytes, void* stream);
 /* The same convolutions on the backbone's 16-bit features without the reference's .float() copy
  * (msdeformattn.py:320, 336; the conversion is exact, so the results are those of the fp32 calls on
  * the upcast tensor): 1x1 only.  m2f_conv_x3_io mode 0 reads I as i_dtype (M2F_F32 / M2F_F16 /

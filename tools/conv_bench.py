@@ -30,7 +30,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="", help="shapes whose name contains this")
     ap.add_argument("--lib", default=None, help="another build of libbm2f.so (A/B)")
-    ap.add_argument("--x3-only", action="store_true", help="skip the MIOpen timings (A/B runs)")
+    ap.add_argument("--x3-only", action="store_true", help='only the "tn" and "fused" weight-gradient arms (A/B runs)')
+    ap.add_argument("--rounds", type=int, default=1, help="repeat the alternated arms this many times")
     a = ap.parse_args()
     if a.lib:
         from bm2f_amd import _native as _nat
@@ -46,17 +47,27 @@ def main():
         x = torch.randn(N, Ci, H, W, device=dev, requires_grad=True)
         g = torch.randn(N, Co, H, W, device=dev)
         fl = 2.0 * N * H * W * Ci * Co * k * k
-        res = {}
-        engines = (("miopen", lambda: conv(x)), ("x3", lambda: conv_ops.conv2d(x, conv)),
-                   ("x3+tn", lambda: conv_ops.conv2d(x, conv)))
-        for eng, fn in engines[2:] if a.x3_only else engines:
-            conv_ops.WGRAD3 = "tn" if eng == "x3+tn" else "miopen"
-            tf = timeit(fn)
-            y = fn()
-            tb = timeit(lambda: torch.autograd.grad(y, (x, conv.weight), g, retain_graph=True))
-            res[eng] = (tf, tb)
-        print(f"{name:18s} " + "  ".join(f"{e}: fwd {tf:.3f} ms ({fl / tf / 1e9:.0f} TF) bwd {tb:.3f} ms ({2 * fl / tb / 1e9:.0f} TF)"
-                                         for e, (tf, tb) in res.items()), flush=True)
+        # arms: the library for everything, then the x3 forward / input gradient with each 3x3 weight-gradient
+        # engine of conv_ops.WGRAD3 (1x1 shapes have one x3 weight gradient: the "x3+tn" arm alone)
+        arms = [("miopen", None)] + [("x3+" + e, e) for e in (("miopen", "x3", "tn", "fused") if k == 3 else ("tn",))]
+        if a.x3_only:
+            arms = [arm for arm in arms if arm[1] in ("tn", "fused")]
+        for rnd in range(a.rounds):   # arms alternated inside a round: the spread between rounds is the noise
+            res = {}
+            for eng, wg in arms:
+                fn = (lambda: conv(x)) if wg is None else (lambda: conv_ops.conv2d(x, conv))
+                conv_ops.WGRAD3 = wg or "tn"
+                tf = timeit(fn)
+                y = fn()
+                tb = timeit(lambda: torch.autograd.grad(y, (x, conv.weight), g, retain_graph=True))
+                xd = x.detach()   # no input gradient wanted: the backward is the weight gradient alone
+                yw = conv(xd) if wg is None else conv_ops.conv2d(xd, conv)
+                tw = timeit(lambda: torch.autograd.grad(yw, (conv.weight,), g, retain_graph=True))
+                res[eng] = (tf, tb, tw)
+                del y, yw
+            print(f"{name:18s} round {rnd}  " + "  ".join(
+                f"{e}: fwd {tf:.3f} ms ({fl / tf / 1e9:.0f} TF) bwd {tb:.3f} ms ({2 * fl / tb / 1e9:.0f} TF) "
+                f"wgrad {tw:.3f} ms" for e, (tf, tb, tw) in res.items()), flush=True)
         del x, g, conv
 
 
