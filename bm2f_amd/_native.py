@@ -13,6 +13,7 @@ import ctypes
 import os
 import threading
 
+import numpy as np
 import torch
 
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libbm2f.so")
@@ -245,6 +246,28 @@ def workspace(name: str, *args, device, dtype=torch.uint8, floor: int = 0, unit:
     """The scratch tensor of a ``*_workspace`` query: ``max(n, floor) // unit`` elements of ``dtype`` for the ``n``
     (bytes or words, see bm2f.h) that ``name(*args, &n)`` reports."""
     return torch.empty(max(query(name, *args), floor) // unit, dtype=dtype, device=device)
+
+
+def upload_tables(tables, device):
+    """One host-to-device copy of several int32 / int64 arrays, each on an 8-byte boundary -> {name: tensor}."""
+    parts, spans, at = [], {}, 0
+    for name, arr in tables.items():
+        flat = np.ascontiguousarray(arr).reshape(-1)
+        raw = flat.view(np.int32)
+        if raw.size % 2:
+            raw = np.concatenate((raw, np.zeros(1, np.int32)))
+        spans[name] = (at, flat.size, flat.dtype)
+        parts.append(raw)
+        at += raw.size
+    buf = torch.from_numpy(np.concatenate(parts) if at else np.zeros(2, np.int32)).to(device)
+    out = {}
+    for name, (start, n, dtype) in spans.items():
+        if dtype == np.int64:
+            out[name] = buf[start:start + 2 * n].view(torch.int64)
+        else:
+            out[name] = buf[start:start + n]
+    out["_buffer"] = buf
+    return out
 
 
 def set_option(name: str, value: int) -> None:

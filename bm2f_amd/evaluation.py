@@ -16,6 +16,7 @@ import os
 import numpy as np
 import torch
 
+from .label_planes import as_label_plane, same_dtype
 from .label_rle import label_maps_to_rle, rle_to_label_maps
 from .rle import rle_encode
 
@@ -74,29 +75,10 @@ def instances_to_coco_json(instances, img_id):
 # -------------------------------------------------------------------------------------------------------------------
 # label maps: semantic result files, panoptic and instance-map annotations (bm2f_amd.label_rle)
 # -------------------------------------------------------------------------------------------------------------------
-_LABEL_DTYPES = (torch.uint8, torch.int16, torch.int32)
-
-
 def _label_batch(maps):
     """Integer label maps (tensors or arrays, any integer dtype) -> tensors of one of uint8 / int16 / int32."""
-    out = []
-    for k, m in enumerate(maps):
-        if not torch.is_tensor(m):
-            a = np.asarray(m)
-            if a.dtype.kind not in "iu":
-                raise ValueError(f"label map {k} must hold integers, got {a.dtype}")
-            if a.dtype.name not in ("uint8", "int16", "int32"):
-                if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
-                    raise ValueError(f"label map {k} holds labels beyond int32")
-                a = a.astype(np.int32)
-            m = torch.from_numpy(np.ascontiguousarray(a))
-        elif m.is_floating_point() or m.dtype == torch.bool:
-            raise ValueError(f"label map {k} must hold integers, got {m.dtype}")
-        elif m.dtype not in _LABEL_DTYPES:
-            m = m.to(torch.int32)
-        out.append(m)
-    widest = max((m.dtype for m in out), key=_LABEL_DTYPES.index, default=None)
-    return [m if m.dtype == widest else m.to(widest) for m in out]
+    planes = [as_label_plane(m, f"label map {k}") for k, m in enumerate(maps)]
+    return same_dtype([m if torch.is_tensor(m) else torch.from_numpy(np.ascontiguousarray(m)) for m in planes])
 
 
 def sem_seg_to_coco_json(label_maps, file_names, *, contiguous_id_to_dataset_id=None, ignore=None):

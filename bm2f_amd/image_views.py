@@ -41,13 +41,13 @@ import torch
 
 from . import _native
 from . import color_aug as _ca
+from .label_planes import LABEL_DTYPES
 from .tta import tta_view_sizes
 
 _FIELDS = 20          # include/bm2f.h: M2F_VIEW_FIELDS
 MAX_KSIZE = 131       # include/bm2f.h: M2F_VIEW_MAX_KSIZE: a down-scale of at most 65x per axis
 _PRECISION_BITS = 22  # Pillow Resample.c: PRECISION_BITS = 32 - 8 - 2
 _U8 = 3               # include/bm2f.h: M2F_U8
-_LABEL_DTYPES = (torch.uint8, torch.int16, torch.int32)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -239,7 +239,7 @@ def _span(tensors, extents):
     return base, (end - base) // size, [(t.data_ptr() - base) // size for t in tensors]
 
 
-def _upload(plan, dev):
+def _upload_plan(plan, dev):
     """The view table, the colour table (when there is one) and the axis tables in one buffer, one copy: -> (device
     buffer, rows pointer, tables pointer, colours pointer or None)."""
     V = plan.rows.shape[0]
@@ -346,7 +346,7 @@ def _launch_image(src_ptr, src_numel, plan, rows, out, mean, std, pad_value):
     """rows: plan.rows with the source offsets and strides filled in.  One upload, one launch."""
     dev = out.device
     rows = np.ascontiguousarray(rows, dtype=np.int64)
-    keep, rows_dev, tables_dev, colors_dev = _upload(_with_rows(plan, rows), dev)
+    keep, rows_dev, tables_dev, colors_dev = _upload_plan(_with_rows(plan, rows), dev)
     m, s = ((0.0,) * 3, (1.0,) * 3) if mean is None else (mean.tolist(), std.tolist())
     store = (int(mean is not None), *m, *s, float(pad_value), _out_code(out.dtype), out.data_ptr(), out.shape[2],
              out.shape[3], _native.stream(dev))
@@ -436,7 +436,7 @@ def image_views(images, views, *, pixel_mean=None, pixel_std=None, out_dtype, si
 
 def _launch_label(src_ptr, elem_bytes, src_numel, plan, rows, out):
     dev = out.device
-    keep, rows_dev, tables_dev, _ = _upload(_with_rows(plan, rows), dev)
+    keep, rows_dev, tables_dev, _ = _upload_plan(_with_rows(plan, rows), dev)
     _native.call("m2f_label_views", src_ptr, elem_bytes, src_numel, _host_ptr(rows), rows_dev, rows.shape[0],
                  out.shape[1], tables_dev, plan.tables.size, out.data_ptr(), out.shape[2], out.shape[3],
                  _native.stream(dev))
@@ -454,14 +454,14 @@ def label_views(planes, views, *, seg_pad, size_divisibility=0, out=None):
         raise ValueError("no source planes")
     p0 = planes[0]
     for p in planes:
-        if p.dtype not in _LABEL_DTYPES:
+        if p.dtype not in LABEL_DTYPES:
             raise ValueError(f"label planes must be uint8, int16 or int32, got {p.dtype}")
         if p.dim() != 3 or p.shape[0] != p0.shape[0] or p.dtype != p0.dtype or p.device != p0.device:
             raise ValueError("the sources must be (P, H, W) with one P, dtype and device")
     if p0.shape[0] <= 0:
         raise ValueError("no planes")
-    info = torch.iinfo(p0.dtype)
-    if not info.min <= int(seg_pad) <= info.max:
+    _, lo, hi = LABEL_DTYPES[p0.dtype]
+    if not lo <= int(seg_pad) <= hi:
         raise ValueError(f"seg_pad {seg_pad} does not fit {p0.dtype}")
     views = [dataclasses.replace(v, fill=0, color=None) for v in views]
     plan = _Plan(views, [tuple(p.shape[1:]) for p in planes], image=False)

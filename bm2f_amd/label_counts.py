@@ -31,10 +31,8 @@ import numpy as np
 import torch
 
 from . import _native
-from .mask_iou import _upload
+from .label_planes import np_dtype, reads
 
-_A_DTYPES = (np.uint8, np.int16, np.int32)
-_B_DTYPES = (np.uint8, np.int16, np.int32, np.int64)
 _PATHS = {"auto": 0, "lds": 1, "global": 2}
 _FIELDS = 8                               # M2F_LABEL_IMAGE_FIELDS
 _geometry = None
@@ -53,13 +51,8 @@ MAX_IDS = 1024                            # M2F_LABEL_MAX_IDS
 _INT_MAX = 2 ** 31 - 1
 
 
-def _np_dtype(p):
-    if torch.is_tensor(p):
-        try:
-            return np.dtype(str(p.dtype).replace("torch.", ""))
-        except TypeError:
-            return np.dtype(object)                                   # no label dtype: refused by the caller
-    return np.asarray(p).dtype
+def _dtype(p):
+    return np_dtype(p.dtype if torch.is_tensor(p) else np.asarray(p).dtype)
 
 
 def _per_image(value, n, name):
@@ -104,8 +97,8 @@ def _plan(a_planes, b_planes, rows, cols, ignore, ids, share_output, path):
     a_dt = b_dt = None
     kinds = set()
     for i, (a, b) in enumerate(zip(a_planes, b_planes)):
-        da, db = _np_dtype(a), _np_dtype(b)
-        if da not in _A_DTYPES or db not in _B_DTYPES:
+        da, db = _dtype(a), _dtype(b)
+        if not reads(da) or not reads(db, wide=True):
             raise ValueError(f"image {i}: a must be uint8, int16 or int32 and b uint8, int16, int32 or int64, got "
                              f"{da} and {db}")
         if (a_dt, b_dt) != (None, None) and (da, db) != (a_dt, b_dt):
@@ -234,7 +227,7 @@ def _counts_device(plan):
         assert images.shape[1] == _FIELDS
         blocks = _blocks(a_off, plan["pixels"])
         flat_ids = (np.concatenate(ids) if ids else np.zeros(0, np.int64)).astype(np.int32)
-        dev = _upload({"images": images, "ids": flat_ids, "blocks": blocks}, device)             # one copy
+        dev = _native.upload_tables({"images": images, "ids": flat_ids, "blocks": blocks}, device)  # one copy
         out = torch.zeros(plan["out_len"] + G, dtype=torch.int64, device=device)
         ign = plan["ignore"]
         _native.call("m2f_label_pair_counts_ragged", a_base or None, plan["a_dtype"].itemsize, a_elems, b_base or None,
@@ -303,8 +296,8 @@ def label_histogram_ragged(planes, bins, ignore=None, *, path="auto"):
     rows = bins + 1
     dt, devices = None, set()
     for i, p in enumerate(planes):
-        d = _np_dtype(p)
-        if d not in _A_DTYPES or (dt is not None and d != dt):
+        d = _dtype(p)
+        if not reads(d) or (dt is not None and d != dt):
             raise ValueError(f"image {i}: planes must be uint8, int16 or int32, one dtype per batch, got {d}"
                              + (f" after {dt}" if dt is not None else ""))
         dt = d
@@ -336,7 +329,7 @@ def label_histogram_ragged(planes, bins, ignore=None, *, path="auto"):
                           axis=1).astype(np.int64)
         assert images.shape[1] == _FIELDS
         blocks = _blocks(off, pixels)
-        dev = _upload({"images": images, "blocks": blocks}, device)                              # one copy
+        dev = _native.upload_tables({"images": images, "blocks": blocks}, device)                # one copy
         out = torch.zeros(B * rows + B, dtype=torch.int64, device=device)
         _native.call("m2f_label_histogram_ragged", base or None, dt.itemsize, elems, dev["images"].data_ptr(), B,
                      _native.ptr_or_null(dev["blocks"]), blocks.shape[0], int(ignore is not None), int(ignore or 0),

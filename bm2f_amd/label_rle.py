@@ -22,10 +22,10 @@ import numpy as np
 import torch
 
 from . import _native
-from .mask_iou import _run_ends_chunked, _upload
+from .label_planes import LABEL_DTYPES
+from .mask_iou import _run_ends_chunked
 from .rle import _GROUP_LIMITS, _encode_host, counts_to_string, rle_decode
 
-_DTYPES = {torch.uint8: (1, 0, 255), torch.int16: (2, -2 ** 15, 2 ** 15 - 1), torch.int32: (4, -2 ** 31, 2 ** 31 - 1)}
 _IMAGE_FIELDS, _HEADER_FIELDS, _PAINT_FIELDS = 8, 8, 6          # M2F_LABEL_RLE_*_FIELDS
 _INT32 = (-2 ** 31, 2 ** 31 - 1)
 
@@ -39,7 +39,7 @@ def _check_planes(planes):
     for k, p in enumerate(planes):
         if not torch.is_tensor(p) or p.dim() != 2:
             raise ValueError(f"plane {k} must be a (H, W) tensor")
-        if p.dtype not in _DTYPES:
+        if p.dtype not in LABEL_DTYPES:
             raise ValueError(f"plane {k}: labels must be uint8, int16 or int32, got {p.dtype}")
         if p.dtype != planes[0].dtype:
             raise ValueError(f"planes of different dtypes in one batch: {planes[0].dtype} and {p.dtype}")
@@ -118,7 +118,7 @@ def _segments_device(planes, ignores, ids):
     """planes: HIP tensors of one dtype, each of at least one pixel -> per plane the list of entries."""
     dev = planes[0].device
     B = len(planes)
-    nbytes, lo, hi = _DTYPES[planes[0].dtype]
+    nbytes, lo, hi = LABEL_DTYPES[planes[0].dtype]
     hw = np.array([p.shape for p in planes], dtype=np.int64)
     pixels = hw[:, 0] * hw[:, 1]
     col_base = np.concatenate(([0], np.cumsum(hw[:, 1])))
@@ -134,7 +134,7 @@ def _segments_device(planes, ignores, ids):
         keys = sorted({_key(i, v) for i, one in enumerate(ids) for v in one if _INT32[0] <= v <= _INT32[1]})
         tables["seg_key"] = np.array(keys + [0], dtype=np.int64)     # never empty
         tables["num_segments"] = np.array([len(keys)], dtype=np.int64)
-    t = _upload(tables, dev)                                          # the one upload
+    t = _native.upload_tables(tables, dev)                            # the one upload
     st = _native.stream(dev)
     total_cols, num_blocks = int(col_base[-1]), int(block_base[-1])
     with torch.cuda.device(dev):
@@ -268,9 +268,9 @@ def rle_to_label_maps(segments, sizes, *, fill=0, dtype=torch.int32, device=None
     Raises ValueError, before any launch, for a segment whose size is not its image's, counts that do not add up, a
     malformed string, and a value or ``fill`` that does not fit ``dtype``."""
     device = torch.device("cpu" if device is None else device)
-    if dtype not in _DTYPES:
+    if dtype not in LABEL_DTYPES:
         raise ValueError(f"dtype must be uint8, int16 or int32, got {dtype}")
-    nbytes, lo, hi = _DTYPES[dtype]
+    nbytes, lo, hi = LABEL_DTYPES[dtype]
     segments = [list(one) for one in segments]
     sizes = [(int(s[0]), int(s[1])) for s in sizes]
     if len(sizes) != len(segments):
@@ -312,8 +312,8 @@ def rle_to_label_maps(segments, sizes, *, fill=0, dtype=torch.int32, device=None
     out_off = np.concatenate(([0], np.cumsum(elems)))
     block_base = np.concatenate(([0], np.cumsum(((hw[:, 1] + 63) // 64) * ((hw[:, 0] + 3) // 4))))
     images = np.stack((hw[:, 0], hw[:, 1], seg0[:-1], seg0[1:], out_off[:-1], block_base[:-1]), axis=1).astype(np.int64)
-    t = _upload({"offsets": offsets, "images": images, "positions": positions,
-                 "values": np.array(values, dtype=np.int32)}, device)          # the one upload
+    t = _native.upload_tables({"offsets": offsets, "images": images, "positions": positions,
+                               "values": np.array(values, dtype=np.int32)}, device)  # the one upload
     out = torch.empty(int(out_off[-1]), dtype=dtype, device=device)
     if int(block_base[-1]):
         with torch.cuda.device(device):

@@ -28,25 +28,9 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import _native
 from .label_counts import label_histogram_ragged
-from .mask_iou import _upload
-
-_MAP_DTYPES = (torch.uint8, torch.int16, torch.int32)
-_INT_DTYPES = _MAP_DTYPES + (torch.int8, torch.int64)
-
-
-def as_label_maps(maps, what="label_map"):
-    """The maps in a form the kernels read in place: (H, W) integer tensors of one dtype among uint8, int16 and int32,
-    contiguous.  Maps that already share such a dtype are kept as they are; otherwise every map is converted to
-    int32, once (int64, what the reference's mappers ship, lands here)."""
-    maps = [m if torch.is_tensor(m) else torch.as_tensor(np.asarray(m)) for m in maps]
-    for b, m in enumerate(maps):
-        if m.dim() != 2 or m.dtype not in _INT_DTYPES:
-            raise ValueError(f"{what} of image {b} must be an (H, W) integer tensor, got {tuple(m.shape)} {m.dtype}")
-    dtypes = {m.dtype for m in maps}
-    if len(dtypes) == 1 and maps[0].dtype in _MAP_DTYPES:
-        return [m.contiguous() for m in maps]
-    return [m.to(torch.int32).contiguous() for m in maps]
+from .label_planes import as_label_maps                     # mask_criterion imports it from here
 
 
 def _device_of(maps):
@@ -62,7 +46,7 @@ def _id_tables(per_image, device):
     names = list(per_image[0]) if per_image else []
     flat = {k: np.concatenate([p[k] for p in per_image]).astype(np.int32 if k == "ids" else np.int64) for k in names}
     if device.type == "cuda":
-        dev = _upload(flat, device)                                                              # one copy
+        dev = _native.upload_tables(flat, device)                                                # one copy
     else:
         dev = {k: torch.from_numpy(v) for k, v in flat.items()}
     out, at = [], 0

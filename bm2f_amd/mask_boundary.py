@@ -35,7 +35,7 @@ import torch
 
 from . import _native
 from .mask_iou import (MAX_RAGGED_WORDS, _check_size, _decode_plan, _groups_by_offset, _launch_decode, _launch_pairs,
-                       _pack_rows, _pair_counts_ragged_host, _pair_plan, _split_counts, _upload, rle_to_bits_ragged)
+                       _pack_rows, _pair_counts_ragged_host, _pair_plan, _split_counts, rle_to_bits_ragged)
 from .polygon import _crossings_host, _decode_host, _launch_polygons, _plan, _tables, is_polygon
 
 
@@ -170,7 +170,7 @@ def boundary_bits_ragged(words, offsets, sizes, dilation_ratio=0.02, dilations=N
     tables, num_blocks = _boundary_plan(hw, offsets, d, words.numel())
     if words.device.type != "cuda":
         return torch.from_numpy(_boundary_host(words.detach().numpy(), hw, offsets, d)).to(words.device)
-    dev = _upload(tables, words.device)                               # one copy
+    dev = _native.upload_tables(tables, words.device)                 # one copy
     out = torch.empty_like(words)
     _launch_boundary(words.detach(), out, dev, offsets.size, num_blocks, int(d.max()), words.device)
     return out
@@ -235,7 +235,7 @@ def boundary_pair_counts_ragged(masks, groups, device=None, sizes=None, names=No
         edges = _boundary_host(words, hw, out_offsets, d)
         return _pair_counts_ragged_host(words, desc, ptables), _pair_counts_ragged_host(edges, desc, ptables)
     poly_tables = _tables(plan, out_offsets[which]) if plan is not None else {}
-    dev = _upload({**dtables, **poly_tables, **ptables, **btables}, device)      # one copy
+    dev = _native.upload_tables({**dtables, **poly_tables, **ptables, **btables}, device)  # one copy
     words = torch.empty(total, dtype=torch.int32, device=device)
     edges = torch.empty(total, dtype=torch.int32, device=device)
     _launch_decode(dev, len(rles), words, device)

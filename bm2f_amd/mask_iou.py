@@ -169,7 +169,7 @@ def rle_to_bits(rles, device=None, size=None) -> torch.Tensor:
     M = len(rles)
     if device.type != "cuda":
         return torch.from_numpy(_decode_host(positions, offsets, H, W)).to(device)
-    dev = _upload({"offsets": offsets, "positions": positions}, device)      # one copy
+    dev = _native.upload_tables({"offsets": offsets, "positions": positions}, device)  # one copy
     off, pos = dev["offsets"], dev["positions"]
     out = torch.empty((M, H, (W + 31) // 32), dtype=torch.int32, device=device)
     st = _native.stream(device)
@@ -343,28 +343,6 @@ def _decode_plan(rles, sizes):
     return hw, out_offsets, total, tables
 
 
-def _upload(tables, device):
-    """One host-to-device copy of several int32 / int64 arrays, each on an 8-byte boundary -> {name: tensor}."""
-    parts, spans, at = [], {}, 0
-    for name, arr in tables.items():
-        flat = np.ascontiguousarray(arr).reshape(-1)
-        raw = flat.view(np.int32)
-        if raw.size % 2:
-            raw = np.concatenate((raw, np.zeros(1, np.int32)))
-        spans[name] = (at, flat.size, flat.dtype)
-        parts.append(raw)
-        at += raw.size
-    buf = torch.from_numpy(np.concatenate(parts) if at else np.zeros(2, np.int32)).to(device)
-    out = {}
-    for name, (start, n, dtype) in spans.items():
-        if dtype == np.int64:
-            out[name] = buf[start:start + 2 * n].view(torch.int64)
-        else:
-            out[name] = buf[start:start + n]
-    out["_buffer"] = buf
-    return out
-
-
 def _launch_decode(dev_tables, num_masks, words, device):
     t = dev_tables
     with torch.cuda.device(device):
@@ -397,7 +375,7 @@ def rle_to_bits_ragged(rles, device=None, sizes=None):
             plane = _decode_host(pos[off[m]:off[m + 1]], np.array([0, off[m + 1] - off[m]]), int(H), int(W))
             words[out_offsets[m]:out_offsets[m] + plane.size] = plane.reshape(-1)
         return torch.from_numpy(words).to(device), out_offsets, hw
-    dev = _upload(tables, device)
+    dev = _native.upload_tables(tables, device)
     words = torch.empty(total, dtype=torch.int32, device=device)
     _launch_decode(dev, len(rles), words, device)
     return words, out_offsets, hw
@@ -505,7 +483,7 @@ def mask_pair_counts_ragged(words, groups):
     desc, tables, num_tiles = _pair_plan(groups, words.numel())
     if words.device.type != "cuda":
         return _pair_counts_ragged_host(words.detach().numpy(), desc, tables)
-    dev = _upload(tables, words.device)
+    dev = _native.upload_tables(tables, words.device)
     out = _launch_pairs(words.detach(), desc, dev, num_tiles, words.device)
     return _split_counts(out.cpu().numpy(), desc)                     # the one copy
 
@@ -542,7 +520,7 @@ def rle_pair_counts_ragged(rles, groups, device=None, sizes=None):
     if device.type != "cuda":
         words = rle_to_bits_ragged(rles, device, sizes)[0]
         return _pair_counts_ragged_host(words.numpy(), desc, ptables)
-    dev = _upload({**dtables, **ptables}, device)
+    dev = _native.upload_tables({**dtables, **ptables}, device)
     words = torch.empty(total, dtype=torch.int32, device=device)
     _launch_decode(dev, len(rles), words, device)
     out = _launch_pairs(words, desc, dev, num_tiles, device)

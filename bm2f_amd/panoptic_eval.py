@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from .label_counts import MAX_IDS, label_pair_counts_ragged
+from .label_planes import as_label_plane, integer_plane, same_dtype
 
 VOID = 0
 MAX_PRED_ID = 65536                    # columns are 0 .. the largest predicted id: (1025 rows) x 2^16 counters at most
@@ -240,45 +241,13 @@ class PanopticGroundTruth:
             from PIL import Image                                     # only this route needs PIL
             with Image.open(os.path.join(self.png_root, ann["file_name"])) as im:
                 m = rgb2id(np.asarray(im.convert("RGB"), dtype=np.uint8))
-        if torch.is_tensor(m):
-            if m.is_floating_point() or m.dtype == torch.bool:
-                raise ValueError(f"image {image_id!r}: the id map must hold integers")
-            return m.to(torch.int32)
-        m = np.asarray(m)
-        if m.dtype.kind not in "iu":
-            raise ValueError(f"image {image_id!r}: the id map must hold integers")
-        return m.astype(np.int32)
+        m = integer_plane(m, f"image {image_id!r}: the id map")
+        return m.to(torch.int32) if torch.is_tensor(m) else m.astype(np.int32)
 
 
 # -------------------------------------------------------------------------------------------------------------------
 # evaluation
 # -------------------------------------------------------------------------------------------------------------------
-def _pred_plane(id_map, device):
-    """The head's id map -> an integer plane the kernel takes (int32 as the head returns it), on ``device`` if given."""
-    if torch.is_tensor(id_map):
-        if id_map.is_floating_point() or id_map.dtype == torch.bool:
-            raise ValueError("panoptic_seg must be an integer id map")
-        if id_map.dtype not in (torch.uint8, torch.int16, torch.int32, torch.int64):
-            id_map = id_map.to(torch.int32)
-        return id_map.to(device) if device is not None else id_map
-    m = np.asarray(id_map)
-    if m.dtype.kind not in "iu":
-        raise ValueError("panoptic_seg must be an integer id map")
-    if m.dtype not in (np.uint8, np.int16, np.int32, np.int64):
-        m = m.astype(np.int64)
-    return torch.from_numpy(np.ascontiguousarray(m)).to(device) if device is not None else m
-
-
-def _same_dtype(planes):
-    """Planes of mixed integer dtypes -> all as the widest (a batch is counted in one dtype per side)."""
-    def name(p):
-        return str(p.dtype).replace("torch.", "")
-    widest = max((name(p) for p in planes), key=lambda n: np.dtype(n).itemsize, default=None)
-    if all(name(p) == widest for p in planes):
-        return planes
-    return [p.to(getattr(torch, widest)) if torch.is_tensor(p) else p.astype(widest) for p in planes]
-
-
 def panoptic_counts(gt, items, device=None, path="auto"):
     """items: ``(image_id, id_map, segments_info)`` per image, ``segments_info`` with dataset category ids.  -> one
     ``(table, gt_segments, gt_rows)`` per image: one launch of the counting kernel for the whole batch (the numpy
@@ -288,7 +257,9 @@ def panoptic_counts(gt, items, device=None, path="auto"):
     for image_id, id_map, segments_info in items:
         segs = gt.segments(image_id)
         a = gt.id_map(image_id)
-        b = _pred_plane(id_map, device)
+        b = as_label_plane(id_map, "panoptic_seg", wide=True)
+        if device is not None:
+            b = (b if torch.is_tensor(b) else torch.from_numpy(np.ascontiguousarray(b))).to(device)
         if tuple(a.shape) != tuple(b.shape):
             raise ValueError(f"image {image_id!r}: the prediction is {tuple(b.shape)}, the ground truth {tuple(a.shape)}")
         order = sorted(range(len(segs)), key=lambda k: segs[k]["id"])
@@ -308,7 +279,7 @@ def panoptic_counts(gt, items, device=None, path="auto"):
         metas.append((image_id, segs, gt_rows))
     if not metas:
         return []
-    tables, bad = label_pair_counts_ragged(_same_dtype(a_planes), _same_dtype(b_planes), rows=rows, cols=cols,
+    tables, bad = label_pair_counts_ragged(same_dtype(a_planes), same_dtype(b_planes), rows=rows, cols=cols,
                                            ids=id_lists, path=path)
     for k in np.flatnonzero(bad).tolist():
         # the error path alone reads a prediction back: name the first id that is not a column

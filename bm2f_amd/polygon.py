@@ -42,7 +42,7 @@ import torch
 from . import _native
 from .mask_iou import (_PLANE_ALIGN, MAX_RAGGED_WORDS, _check_size, _decode_plan, _groups_by_offset, _launch_decode,
                        _launch_pairs, _pack_rows, _pair_counts_ragged_host, _pair_plan, _plane_words, _split_counts,
-                       _upload, rle_pair_counts_ragged, rle_to_bits_ragged)
+                       rle_pair_counts_ragged, rle_to_bits_ragged)
 from .rle import counts_to_string, rle_encode
 
 MAX_COORD = 2.0 ** 26                   # |x|, |y| below this keep 5 x + 0.5 and the edge lengths inside int32
@@ -249,7 +249,7 @@ def _launch_polygons(t, plan, words, device):
 def _rasterize(plan, out_offsets, total_words, device):
     if device.type != "cuda":
         return torch.from_numpy(_decode_host(_crossings_host(plan), plan, out_offsets, total_words)).to(device)
-    dev = _upload(_tables(plan, out_offsets), device)                 # one copy
+    dev = _native.upload_tables(_tables(plan, out_offsets), device)   # one copy
     words = torch.empty(total_words, dtype=torch.int32, device=device)
     _launch_polygons(dev, plan, words, device)
     return words
@@ -273,7 +273,7 @@ def polygon_crossings(polys, sizes, device=None):
         return torch.from_numpy(_crossings_host(plan)).to(device), plan.pos_offsets
     if plan.total == 0:
         return torch.zeros(0, dtype=torch.int32, device=device), plan.pos_offsets
-    dev = _upload(_tables(plan, np.zeros(plan.num_anns, np.int64)), device)
+    dev = _native.upload_tables(_tables(plan, np.zeros(plan.num_anns, np.int64)), device)
     return _sorted_positions(dev, plan, device), plan.pos_offsets
 
 
@@ -414,7 +414,7 @@ def pair_counts_ragged(masks, groups, device=None, sizes=None, names=None):
         words = rle_to_bits_ragged(rles, device, sizes)[0].numpy()    # zero planes where the polygons go
         words = words | _decode_host(_crossings_host(plan), plan, out_offsets[which], total)
         return _pair_counts_ragged_host(words, desc, ptables)
-    dev = _upload({**dtables, **_tables(plan, out_offsets[which]), **ptables}, device)
+    dev = _native.upload_tables({**dtables, **_tables(plan, out_offsets[which]), **ptables}, device)
     words = torch.empty(total, dtype=torch.int32, device=device)
     _launch_decode(dev, len(rles), words, device)
     _launch_polygons(dev, plan, words, device)

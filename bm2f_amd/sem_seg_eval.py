@@ -26,33 +26,8 @@ import numpy as np
 import torch
 
 from .label_counts import label_pair_counts_ragged
+from .label_planes import as_label_plane, same_dtype
 from .panoptic_eval import PQStat, pq_from_counts
-
-
-def _label_plane(x, what, wide_ok):
-    """An integer label map -> an array or tensor of a dtype the kernel takes (no copy when it already is one)."""
-    allowed = ("uint8", "int16", "int32", "int64") if wide_ok else ("uint8", "int16", "int32")
-    if torch.is_tensor(x):
-        name = str(x.dtype).replace("torch.", "")
-        if x.is_floating_point() or x.dtype == torch.bool:
-            raise ValueError(f"{what} must hold integer labels, got {x.dtype}")
-        return x if name in allowed else x.to(torch.int32)
-    x = np.asarray(x)
-    if x.dtype.kind not in "iu":
-        raise ValueError(f"{what} must hold integer labels, got {x.dtype}")
-    if x.dtype.name in allowed:
-        return x
-    if x.size and (x.min() < -2 ** 31 or x.max() >= 2 ** 31):
-        raise ValueError(f"{what} holds labels beyond int32")
-    return x.astype(np.int32)
-
-
-def _widest(planes):
-    def name(p):
-        return str(p.dtype).replace("torch.", "")
-    widest = max((name(p) for p in planes), key=lambda n: np.dtype(n).itemsize)
-    return [p if name(p) == widest else (p.to(getattr(torch, widest)) if torch.is_tensor(p) else p.astype(widest))
-            for p in planes]
 
 
 def sem_seg_metrics(conf_matrix, class_names=None):
@@ -140,11 +115,11 @@ class SemSegEvaluator:
 
     def _ground_truth(self, inp):
         if "sem_seg" in inp:
-            return _label_plane(inp["sem_seg"], "sem_seg", wide_ok=False)
+            return as_label_plane(inp["sem_seg"], "sem_seg")
         if "sem_seg_file_name" in inp:
             from PIL import Image                                     # only this route needs PIL
             with Image.open(inp["sem_seg_file_name"]) as im:
-                return _label_plane(np.asarray(im), "sem_seg_file_name", wide_ok=False)
+                return as_label_plane(np.asarray(im), "sem_seg_file_name")
         raise KeyError("an input needs 'sem_seg' or 'sem_seg_file_name'")
 
     def _prediction(self, out):
@@ -155,7 +130,7 @@ class SemSegEvaluator:
             pred = scores.argmax(0) if torch.is_tensor(scores) else np.asarray(scores).argmax(0)
         else:
             raise KeyError("an output needs 'sem_seg_labels' or 'sem_seg'")
-        return _label_plane(pred, "the prediction", wide_ok=True)
+        return as_label_plane(pred, "the prediction", wide=True)
 
     def _name(self, inp, k):
         for key in ("file_name", "sem_seg_file_name", "image_id"):
@@ -180,8 +155,8 @@ class SemSegEvaluator:
             gts.append(gt)
             preds.append(pred)
         n = self.num_classes + 1
-        tables, bad = label_pair_counts_ragged(_widest(gts), _widest(preds), rows=n, cols=n, ignore=self.ignore_label,
-                                               share_output=not self.with_pq)
+        tables, bad = label_pair_counts_ragged(same_dtype(gts), same_dtype(preds), rows=n, cols=n,
+                                               ignore=self.ignore_label, share_output=not self.with_pq)
         if bad.any():
             k = int(np.flatnonzero(bad)[0])
             raise ValueError(f"image {self._name(inputs[k], k)}: {int(bad[k])} pixels hold a ground-truth label outside "

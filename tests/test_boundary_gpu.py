@@ -2,7 +2,6 @@
 tests/boundary_ref.py, bit for bit, on the cases of tests/boundary_cases.py, and Boundary AP on the device against its
 CPU run and the fixtures.  Every comparison is bit or integer equality."""
 import copy
-import importlib
 
 import numpy as np
 import pytest
@@ -19,7 +18,6 @@ from polygon_cases import polygon_ground_truth
 pytestmark = pytest.mark.gpu
 
 FIXTURE = load_fixture()
-mb = importlib.import_module("bm2f_amd.mask_boundary")
 
 
 @pytest.mark.parametrize("group", list(checks.GROUPS))
@@ -122,7 +120,7 @@ def test_launches_and_copies_do_not_grow_with_the_batch(device, monkeypatch):
         res = [r for r in results if r["image_id"] in images]
         calls, counts = [], {"uploads": 0, "copies": 0}
         with monkeypatch.context() as mp:
-            real_call, real_upload, real_cpu = _native.call, mb._upload, torch.Tensor.cpu
+            real_call, real_upload, real_cpu = _native.call, _native.upload_tables, torch.Tensor.cpu
             mp.setattr(_native, "call", lambda name, *a: calls.append(name) or real_call(name, *a))
 
             def upload(tables, dev):
@@ -132,7 +130,7 @@ def test_launches_and_copies_do_not_grow_with_the_batch(device, monkeypatch):
             def cpu(t, *a, **k):
                 counts["copies"] += t.device.type == "cuda"
                 return real_cpu(t, *a, **k)
-            mp.setattr(mb, "_upload", upload)
+            mp.setattr(_native, "upload_tables", upload)
             mp.setattr(torch.Tensor, "cpu", cpu)
             evaluate_coco(COCOGroundTruth(sub), res, iou_type="boundary", device=device)
         seen.append((calls, counts["uploads"], counts["copies"]))

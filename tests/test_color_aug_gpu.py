@@ -131,7 +131,7 @@ def test_view_sums_equal_the_integer_sum(device):
     rows = plan.rows.copy()
     rows[:, 3] = 3 * cc.GEO_SOURCE[1]
     t = torch.from_numpy(src).to(device)
-    keep, rows_dev, tables_dev, colors_dev = mod._upload(mod._with_rows(plan, rows), device)
+    keep, rows_dev, tables_dev, colors_dev = mod._upload_plan(mod._with_rows(plan, rows), device)
     colors = np.ascontiguousarray(plan.colors)
     Hp, Wp = plan.padded(0)
     ws = _native.workspace("m2f_image_views_sum_workspace", mod._host_ptr(rows), 3, Hp, Wp, device=device,

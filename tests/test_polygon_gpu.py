@@ -1,7 +1,6 @@
 """The kernels of csrc/polygon.hip on the device against the scalar oracle tests/poly_ref.py, and the evaluator's
 polygons="rasterize" on the device against its CPU run.  Every comparison is exact integer or bit equality."""
 import copy
-import importlib
 
 import numpy as np
 import pytest
@@ -15,9 +14,6 @@ from coco_eval_cases import FIELDS, flatten, load_fixture
 from polygon_cases import edge_cases, many_parts, pack, polygon_ground_truth
 
 pytestmark = pytest.mark.gpu
-
-mi = importlib.import_module("bm2f_amd.mask_iou")                  # the package also exports a function of that name
-pg = importlib.import_module("bm2f_amd.polygon")
 
 
 def _planes(words, offsets, sizes):
@@ -124,7 +120,7 @@ class _Counter:
 
     def __init__(self, monkeypatch):
         self.calls, self.uploads, self.sorts, self.copies = [], 0, 0, 0
-        real_call, real_upload, real_sort, real_cpu = _native.call, mi._upload, torch.sort, torch.Tensor.cpu
+        real_call, real_upload, real_sort, real_cpu = _native.call, _native.upload_tables, torch.sort, torch.Tensor.cpu
 
         def call(name, *args):
             self.calls.append(name)
@@ -143,8 +139,7 @@ class _Counter:
             return real_cpu(t, *args, **kw)
 
         monkeypatch.setattr(_native, "call", call)
-        monkeypatch.setattr(mi, "_upload", upload)
-        monkeypatch.setattr(pg, "_upload", upload)
+        monkeypatch.setattr(_native, "upload_tables", upload)
         monkeypatch.setattr(torch, "sort", sort)
         monkeypatch.setattr(torch.Tensor, "cpu", cpu)
 

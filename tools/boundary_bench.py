@@ -130,7 +130,7 @@ def main():
 
         # the entry point alone on buffers allocated once
         tables, num_blocks = mb._boundary_plan(hw, offsets, d, words.numel())
-        t = mb._upload(tables, dev)
+        t = _native.upload_tables(tables, dev)
         out = torch.empty_like(words)
         st = torch.cuda.current_stream(dev).cuda_stream
         args = (words.data_ptr(), words.numel(), len(rles), t["bd_sizes"].data_ptr(), t["bd_offsets"].data_ptr(),

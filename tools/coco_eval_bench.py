@@ -158,7 +158,7 @@ def main():
                            np.arange(n0 + nd, n0 + nd + ng)))
         hw, offs, total, dtab = mask_iou._decode_plan(rles, None)
         desc, ptab, tiles = mask_iou._pair_plan([(H, W, offs[ia], offs[ib]) for H, W, ia, ib in groups], total)
-        d = mask_iou._upload({**dtab, **ptab}, dev)
+        d = _native.upload_tables({**dtab, **ptab}, dev)
         words = torch.empty(total, dtype=torch.int32, device=dev)
         plane_words = int(mask_iou._plane_words(hw).sum())
         n_inter, n_a, n_b = int((desc[:, 2] * desc[:, 3]).sum()), int(desc[:, 2].sum()), int(desc[:, 3].sum())

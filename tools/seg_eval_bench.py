@@ -41,7 +41,6 @@ sys.path.insert(0, ROOT)
 from bm2f_amd import (COCOPanopticEvaluator, PanopticGroundTruth, SemSegEvaluator,  # noqa: E402
                       label_pair_counts_ragged)
 from bm2f_amd import _native, label_counts  # noqa: E402
-from bm2f_amd.mask_iou import _upload  # noqa: E402
 
 HBM_BYTES_PER_S = 8e12
 OFFSET = 256 ** 3
@@ -101,7 +100,7 @@ def kernel_window(a_planes, b_planes, rows, cols, ignore, ids, share, path, reps
     images = np.stack((off, off, pixels, rows, cols, out_off, id_off, id_n), axis=1).astype(np.int64)
     blocks = label_counts._blocks(off, pixels)
     flat_ids = (np.concatenate([np.asarray(x) for x in ids]) if ids else np.zeros(0)).astype(np.int32)
-    d = _upload({"images": images, "ids": flat_ids, "blocks": blocks}, dev)
+    d = _native.upload_tables({"images": images, "ids": flat_ids, "blocks": blocks}, dev)
     out = torch.zeros(out_len + G, dtype=torch.int64, device=dev)
     args = (fa.data_ptr(), fa.element_size(), fa.numel(), fb.data_ptr(), fb.element_size(), fb.numel(),
             d["images"].data_ptr(), G, _native.ptr_or_null(d["ids"]), flat_ids.size, d["blocks"].data_ptr(),
