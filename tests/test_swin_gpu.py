@@ -9,6 +9,9 @@ op case   B nH  grid   ws shift  reaches
    e      1  2  24x12  12   0    one window column
    f      1  2  10x15   5   2    odd ws, N = 25 -> 32
 
+These reach three of the kernels' eight tile counts (4, 9 and 2 tiles of 16 tokens).  tests/test_window_attn_sweep_gpu.py
+runs every window size 2 .. 12, shifts other than ws // 2, other scales and few windows, with a tighter fp32 bound.
+
 Tolerance: every tensor within max(1e-3, 2 x floor) of its max, where the floor is the torch
 path's own distance from fp64 in the same I/O precision (fp32 softmax in every precision, as autocast runs it).
 """
