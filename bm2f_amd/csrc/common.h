@@ -97,11 +97,26 @@ inline int grid_1d(int64_t nb, const char* fn, unsigned* grid) {
 // Explicit tuning options (m2f_set_option, include/bm2f.h): geometry and engine overrides for tests and
 // tools.  The library never reads the environment; an unset option means the built-in default.  Every
 // option changes the partition or the kernel variant only, never the arithmetic's result.
+// The one list of options: X(enumerator, "name").  enum Option below and the name table of library.hip both
+// come from it, so a new option is one line here.
+#define M2F_OPTIONS(X)                                                                                          \
+  X(kOptMsdaThreads, "msda_threads") X(kOptMsdaTile, "msda_tile") X(kOptMsdaTileW, "msda_tile_w")               \
+  X(kOptMsdaHalo, "msda_halo") X(kOptMsdaWinRows, "msda_win_rows") X(kOptMsdaBwdTiled, "msda_bwd_tiled")        \
+  X(kOptMsdaFwdTiled, "msda_fwd_tiled") X(kOptMattnDqAtomic, "mattn_dq_atomic") X(kOptGemmNtCfg, "gemm_nt_cfg") \
+  X(kOptX3TnNw, "x3_tn_nw") X(kOptX3TnBlocks, "x3_tn_blocks") X(kOptX3NtCfg, "x3_nt_cfg")                       \
+  X(kOptMsdaFwdQuad, "msda_fwd_quad") X(kOptMsdaBwdOverlap, "msda_bwd_overlap") X(kOptMsdaBwdDet, "msda_bwd_det") \
+  X(kOptMsdaFwdPb, "msda_fwd_pb") X(kOptMsdaBwdRatio, "msda_bwd_ratio") X(kOptMsdaFwdLds, "msda_fwd_lds")       \
+  X(kOptMsdaFwdTile, "msda_fwd_tile") X(kOptMsdaFwdTileW, "msda_fwd_tile_w") X(kOptMsdaFwdCap, "msda_fwd_cap")  \
+  X(kOptMsdaFwdHalo, "msda_fwd_halo") X(kOptMattnFwdMinblk, "mattn_fwd_minblk")                                 \
+  X(kOptMattnBwdMinblk, "mattn_bwd_minblk") X(kOptMaskDfStage, "mask_df_stage")                                 \
+  X(kOptMattnBwdKeys, "mattn_bwd_keys") X(kOptMattnXcd, "mattn_xcd") X(kOptMattnCombine, "mattn_combine")       \
+  X(kOptMsdaBwdRowSort, "msda_bwd_rowsort") X(kOptMsdaBwdWalk4, "msda_bwd_walk4") X(kOptMsdaFwdXcd, "msda_fwd_xcd") \
+  X(kOptMsdaFwdPair, "msda_fwd_pair") X(kOptInferVideoCap, "infer_video_cap")
 enum Option : int {
-  kOptMsdaThreads, kOptMsdaTile, kOptMsdaTileW, kOptMsdaHalo, kOptMsdaWinRows, kOptMsdaBwdTiled, kOptMsdaFwdTiled,
-  kOptMattnDqAtomic, kOptGemmNtCfg, kOptX3TnNw, kOptX3TnBlocks, kOptX3NtCfg, kOptMsdaFwdQuad, kOptMsdaBwdOverlap, kOptMsdaBwdDet, kOptMsdaFwdPb, kOptMsdaBwdRatio,
-  kOptMsdaFwdLds, kOptMsdaFwdTile, kOptMsdaFwdTileW, kOptMsdaFwdCap, kOptMsdaFwdHalo,
-  kOptMattnFwdMinblk, kOptMattnBwdMinblk, kOptMaskDfStage, kOptMattnBwdKeys, kOptMattnXcd, kOptMattnCombine, kOptMsdaBwdRowSort, kOptMsdaBwdWalk4, kOptMsdaFwdXcd, kOptMsdaFwdPair, kOptInferVideoCap, kOptCount
+#define M2F_OPTION_ENUM(id, name) id,
+  M2F_OPTIONS(M2F_OPTION_ENUM)
+#undef M2F_OPTION_ENUM
+  kOptCount
 };
 int64_t option_raw(Option o);  // -1 when unset
 

@@ -7,7 +7,7 @@
 //   - point_sample.hip's sigmoid / softplus (expf / log1pf with an IEEE divide: the mask criterion's own bars);
 //   - decoder.hip's wave_sum16 / wave_max16 and window_attn.hip's wave_sum4 / wave_max4 (partial reductions on
 //     the permlane-swap path, not the 64-lane sum);
-//   - block_sum of gnorm.hip and msda.hip: gnorm's barriers sit before the LDS write and before the read (fp64,
+//   - block_sum of gnorm.hip and msda_generic.hip: gnorm's barriers sit before the LDS write and before the read (fp64,
 //     fixed 256 threads), msda's after the write and after the read (templated type and block size), so the two
 //     make different promises about when `red` may be reused -- they are not one function.
 #pragma once

@@ -1,4 +1,6 @@
-// Device helpers shared by the MSDA kernels (msda.hip, msda_fused.hip).  Header-only, internal.
+// Device helpers and kernel-argument structures shared by the MSDA kernel files (msda_generic.hip,
+// msda_bwd_tiled.hip, msda_fwd_quad.hip, msda_fwd_lds.hip).  Header-only, internal; the host side of those files
+// (launchers, geometry builders) is declared in msda_host.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -106,6 +108,19 @@ struct TileGeom {
   int walk4;      // backward: phase-3 records four per step, decoded once per quad (1) or two per step (0)
   int xcdmap;     // forward: block b's (tile, head) from XCD b % 8 (a contiguous tile range per XCD, all heads of a
                   // tile on one XCD) (1) or the head fastest (0)
+};
+
+// Fused-front-end inputs (raw projection + reference points).
+struct FrontEnd {
+  const float* proj;   // (N, Lq, ld): offsets (M, L, P, 2) then logits (M, L*P); hm: per head m a record
+                       // [offsets (L, P, 2) | logits (L*P)] (m2f_msda_fused_*_hm_f32); grad_proj alike
+  int ld;
+  const float* ref;    // (N or broadcast, Lq, L, 2) [x, y]
+  int64_t ref_bs;      // batch stride of ref in elements (0 = broadcast)
+  int hm;
+  // where head m's offsets / logits start in a projection (or grad_proj) row (LP = L * P)
+  __device__ __forceinline__ int off0(int m, int LP) const { return hm ? m * 3 * LP : m * LP * 2; }
+  __device__ __forceinline__ int lg0(int m, int M, int LP) const { return hm ? m * 3 * LP + 2 * LP : M * LP * 2 + m * LP; }
 };
 
 __device__ __forceinline__ int tile_lo(int t, int n, int nt) { return (t * n) / nt; }

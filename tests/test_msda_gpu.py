@@ -343,7 +343,8 @@ def test_fused_front_end_matches_unfused(device, monkeypatch, shapes):
                                               (1, 2, 1, 1)])
 def test_fused_forward_variants_vs_oracle(device, shapes, quad, pb, lds, pair):
     """The fused forward (m2f_msda_fused_fwd_f32) in its LDS-window forms (value windows staged in LDS per tile and
-    level; a lane quad per query, the default, or two lanes per query, opt-in with msda_fwd_pair=1), its quad form (a lane quad per (query, head), point geometry by DPP broadcast,
+    level: the lane-quad kernel, a quad of lanes per query, is the default; the pair kernel, two lanes per query, is
+    opt-in with msda_fwd_pair=1), its quad form (a lane quad per (query, head), point geometry by DPP broadcast,
     out-of-range points skipped by the exec mask; 1, 2 or 4 points per load batch) and its 8-lane form, against
     the C oracle on the loc / attn the reference front end derives from the same projection: power-of-two and odd
     level shapes (tile edges), 1-4 levels, 5 % of the samples thrown far (out of the level and out of range)."""

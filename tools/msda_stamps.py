@@ -2,8 +2,8 @@
 
     python tools/msda_stamps.py [--build] [--n 16]
 
-Builds tools/lib/libbm2f_diag.so from bm2f_amd/csrc (msda.hip with -DM2F_DIAG) when --build is given (on the CPU
-container), then on the GPU runs the stamped kernel at config 2 shapes (reference-init sampling, as
+Builds tools/lib/libbm2f_diag.so from bm2f_amd/csrc (DIAG_SOURCES below, with -DM2F_DIAG) when --build is given (on the
+CPU container), then on the GPU runs the stamped kernel at config 2 shapes (reference-init sampling, as
 tools/msda_bench.py) and prints, over workgroups, the median cycles of each phase and the kernel time.  The
 stamped build adds one barrier; read its shares, not its length.
 """
@@ -15,14 +15,17 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "tools", "lib", "libbm2f_diag.so")
+# the tiled backward with its stamped entry point (m2f_diag_msda_bwd_stamps_f32), and what it links against: the
+# error string and options (library.hip), m2f::zero_async (eltwise.hip)
+DIAG_SOURCES = ["msda_bwd_tiled.hip", "library.hip", "eltwise.hip"]
 
 
 def build():
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
     csrc = os.path.join(ROOT, "bm2f_amd", "csrc")
     cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950", "-DM2F_DIAG",
-           "-munsafe-fp-atomics", "-I" + os.path.join(ROOT, "include"), "-I" + csrc, os.path.join(csrc, "msda.hip"),
-           os.path.join(csrc, "eltwise.hip"), "-o", LIB]   # eltwise.hip: m2f::zero_async
+           "-munsafe-fp-atomics", "-I" + os.path.join(ROOT, "include"), "-I" + csrc,
+           *(os.path.join(csrc, f) for f in DIAG_SOURCES), "-o", LIB]
     subprocess.run(cmd, check=True)
 
 
